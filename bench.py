@@ -2,7 +2,7 @@
 """Benchmark of the SuperGlue hot path on MI355X: matched image-pairs / second.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C1|C3|C4|C5] [--batch PAIRS_PER_GPU | --global-batch PAIRS]
-                    [--no-cpu-baseline]
+                    [--no-cpu-baseline] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torch.distributed environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one process per GPU,
@@ -471,6 +471,59 @@ def _training_step(dev, B=4, N=1024, iters=20, steps=5):
         return {"error": f"{type(e).__name__}: {e}"[:300]}
 
 
+DUMP_MAX_BYTES = 64_000_000      # --dump-outputs: every file of the directory together
+DUMP_SEED = 0
+
+
+def _output_arrays(obj, name=()):
+    """name -> tensor for what a caller of the timed path receives: dict keys, and pair<i> for the per-pair list of the ragged path."""
+    if torch.is_tensor(obj):
+        return {"_".join(name): obj}
+    found = {}
+    if isinstance(obj, dict):
+        for k, v in obj.items():
+            found.update(_output_arrays(v, name + (str(k),)))
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            found.update(_output_arrays(v, name + (f"pair{i:03d}",)))
+    return found
+
+
+def _dump_plan(arrays):
+    """The size cap of --dump-outputs: DUMP_MAX_BYTES shared out evenly, smallest array first (what a small array leaves goes to the larger
+    ones).  -> [(name, stored dtype, draws)]: draws None = the whole array; otherwise it is stored as the values at the sample positions
+    np.unique(np.random.default_rng(DUMP_SEED).integers(0, numel, size=draws)) of its flattened elements -- the same in every run and every
+    build of the same shapes."""
+    import numpy as np
+    kinds = {k: np.dtype(np.float32 if t.is_floating_point() else np.float64) for k, t in arrays.items()}
+    order = sorted(arrays, key=lambda k: arrays[k].numel() * kinds[k].itemsize)
+    budget = DUMP_MAX_BYTES - 4096 * len(order)                # .npy headers
+    plan = []
+    for i, k in enumerate(order):
+        share = budget // (len(order) - i)
+        n = arrays[k].numel()
+        draws = None if n * kinds[k].itemsize <= share else share // kinds[k].itemsize
+        plan.append((k, kinds[k], draws))
+        budget -= (n if draws is None else draws) * kinds[k].itemsize
+    return plan
+
+
+def dump_outputs(out, dirname):
+    """--dump-outputs: the arrays of `out` as <dirname>/<name>.npy, floating point as float32 and integers (match indices) as float64, both
+    exact; arrays beyond their share of the size cap as a fixed sample (_dump_plan)."""
+    import numpy as np
+    arrays = _output_arrays(out)
+    os.makedirs(dirname, exist_ok=True)
+    for k, kind, draws in _dump_plan(arrays):
+        t = arrays[k].detach()
+        if draws is None:
+            a = t.cpu().numpy().astype(kind)
+        else:
+            pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), size=draws))
+            a = t.reshape(-1).index_select(0, torch.from_numpy(pos).to(t.device)).cpu().numpy().astype(kind)
+        np.save(os.path.join(dirname, f"{k}.npy"), a)
+
+
 def _measure(step, step_compute, args, dist_on, dev):
     """The part of a bench run EVERY rank executes, in this order: the timed region, the per-step spread, the per-rank times of the rccl block.
     `step` holds the collective when N > 1, so nothing here may run on rank 0 alone (round 4 computed the spread inside `if rank == 0`: with more
@@ -511,7 +564,7 @@ def bench_ragged(args, world, rank, dev, dist_on=False):
             return sharding.match_sharded_ragged(match_mine, lens, costs, dst=0, always_collective=True, device=dev)
         return match_mine(mine)
 
-    dt, _, spread, rccl = _measure(step, lambda: match_mine(mine), args, dist_on, dev)
+    dt, out, spread, rccl = _measure(step, lambda: match_mine(mine), args, dist_on, dev)
     if rank == 0:
         res = match_mine(mine)
         my_lens = [lens[i] for i in mine]
@@ -544,6 +597,8 @@ def bench_ragged(args, world, rank, dev, dist_on=False):
             line["cpu_baseline"]["sample"] += f" [one {mm}x{nn_}-keypoint pair = the mean size of the ragged job]"
         else:
             line["cpu_baseline"] = None
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         _flush_c_stdio()              # RCCL's version banner sits in the C library's stdout buffer: get it out BEFORE the line, which stays the last one
         print(json.dumps(line), flush=True)
     if dist_on:
@@ -589,6 +644,8 @@ def _dry_run(args, world, rank):
     # the SAME control flow as the real bench (timed region -> spread -> per-rank block, every rank; then rank 0 reports; then the barrier)
     dt, got, spread, rccl = _measure(step, lambda: stub(mine), args, world > 1, dev)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(got, args.dump_outputs)
         ok = all(bool((got["matches0"][i, :lens[i][0]] == i).all()) for i in range(len(lens)))
         print(json.dumps({"metric": "dry run (no GPU, gloo, stub matcher)", "dry_run": True, "n_gpus": world, "steps": args.steps, "global_batch": len(lens),
                           "scaling": "strong" if args.global_batch else "weak", "step_ms_spread": spread, "rccl": rccl,
@@ -609,7 +666,11 @@ def main():
                     help="pairs of the whole job, split evenly over the ranks (BASELINE: C3 256, C4 64, C5 128 over 8 GPUs) -- strong scaling")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-training-step", action="store_true", help="skip the informational training-step leg (C2, N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the run, write what the last timed step returned (rank 0) as DIR/<name>.npy, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _respawn(args)                                   # does not return
@@ -733,6 +794,8 @@ def main():
             line["cpu_baseline"] = cpu_baseline(cfg, sd, kw, m, n)
         else:
             line["cpu_baseline"] = None
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         _flush_c_stdio()              # RCCL's version banner sits in the C library's stdout buffer: get it out BEFORE the line, which stays the last one
         print(json.dumps(line), flush=True)
     if dist_on:

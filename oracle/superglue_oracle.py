@@ -14,8 +14,8 @@ Pinning status: the reference ships NO tests / golden vectors for this path (SUR
 so the oracle is pinned against outputs of the reference itself, generated in the build
 container by importing /root/reference (tests/golden/make_golden.py, committed together with
 the fixtures it wrote).  tests/test_oracle_golden.py checks the oracle against those
-fixtures; tests/test_oracle_vs_reference.py re-checks against the live reference whenever
-/root/reference is present.
+fixtures; tests/test_oracle_vs_reference.py checks it against the reference's outputs on two more
+small cases and its state-dict layout (tests/golden/reference.npz).
 
 `dtype=torch.float64` gives a higher-precision "truth" used to measure the fp32 noise floor.
 `attn_operand_dtype=torch.float16` rounds the QK^T / PV operands the way the HIP attention

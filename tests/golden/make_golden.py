@@ -217,6 +217,43 @@ def layer_cases(cases=None, fname="stage_layers.npz"):
     np.savez_compressed(os.path.join(HERE, fname), **arrays)
 
 
+REFERENCE_FORWARD_CASES = {
+    # name: (config kwargs, m, n): batch 2, weights seed 3, data seed 9 (tests/test_oracle_vs_reference.py)
+    "s6": (dict(descriptor_dim=64, num_stages=2, num_heads=4, num_iters=3, side_info_size=6), 50, 73),
+    "offset": (dict(descriptor_dim=128, num_stages=2, num_heads=4, num_iters=15, side_info_size=1, use_offset=True), 128, 96),
+}
+REFERENCE_LAYOUT_CASES = {
+    # name: config kwargs whose state-dict layout (names in registration order, shapes) the tests pin
+    "h4": dict(descriptor_dim=64, num_stages=2, num_iters=3, side_info_size=6, num_heads=4),
+    "favor": dict(descriptor_dim=64, num_stages=2, num_iters=3, side_info_size=6, num_heads=1, attention="favor_relu"),
+    "favor1": dict(descriptor_dim=64, num_stages=1, num_heads=1, num_iters=3, attention="favor_relu"),
+}
+
+
+def reference_case():
+    """`reference.npz`: the reference's whole forward on two small seeded cases (scores, context descriptors) and its state-dict
+    layout for three configs (repr of [(name, shape), ...], registration order) -- what tests/test_oracle_vs_reference.py and the
+    layout tests of tests/test_boundary_cpu.py compare against."""
+    arrays = {}
+    for name, (kw, m, n) in REFERENCE_FORWARD_CASES.items():
+        cfg = syn.make_config(**kw)
+        sd = syn.make_state_dict(cfg, seed=3)
+        data = syn.make_batch(2, m, n, cfg["descriptor_dim"], cfg["positional_encoding"]["side_info_size"], seed=9)
+        ref = RefSuperGlue(cfg)
+        ref.load_state_dict(sd, strict=True)
+        with torch.no_grad():
+            out = ref.eval()(data)
+        arrays[f"{name}/config_kwargs"] = np.array(repr(kw))
+        arrays[f"{name}/m"], arrays[f"{name}/n"] = m, n
+        arrays[f"{name}/scores"] = out["scores"].numpy()
+        arrays[f"{name}/context_descriptors0"] = out["context_descriptors0"].numpy()
+    for name, kw in REFERENCE_LAYOUT_CASES.items():
+        arrays[f"layout_{name}/config_kwargs"] = np.array(repr(kw))
+        arrays[f"layout_{name}/state_dict"] = np.array(repr([(k, tuple(v.shape)) for k, v in RefSuperGlue(syn.make_config(**kw)).state_dict().items()]))
+    np.savez_compressed(os.path.join(HERE, "reference.npz"), **arrays)
+    print("reference.npz written")
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     torch.set_num_threads(8)
@@ -228,6 +265,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if sys.argv[1:] == ["trained"]:
         trained_case()
+        sys.exit(0)
+    if sys.argv[1:] == ["reference"]:
+        reference_case()
         sys.exit(0)
     only = sys.argv[1:]                      # e.g. `make_golden.py favor`: (re)generate the named cases only
     for name, (kw, m, n, batch, seed, store) in CASES.items():

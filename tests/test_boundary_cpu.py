@@ -14,7 +14,7 @@ from openglue_amd import _lib, synthetic as syn
 from openglue_amd.superglue import SuperGlue
 from oracle import superglue_oracle as orc
 from tests.packed_model import forward_from_packed
-from tests.util import load_case
+from tests.util import load_case, reference_state_dict_layout
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -52,16 +52,15 @@ def test_state_dict_layout_matches_reference_names():
     assert not any(model.load_state_dict(stripped, strict=True))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/models"), reason="reference not mounted")
-def test_state_dict_equals_live_reference():
-    sys.path.insert(0, "/root/reference")
-    from models.superglue.superglue import SuperGlue as Ref
-    for kw in (dict(num_heads=4), dict(num_heads=1, attention="favor_relu")):      # favor_relu: + the projection_matrix buffers
-        cfg = syn.make_config(descriptor_dim=64, num_stages=2, num_iters=3, side_info_size=6, **kw)
-        a, b = Ref(cfg).state_dict(), SuperGlue(cfg).state_dict()
-        assert list(a.keys()) == list(b.keys())          # same names in the same registration order
-        assert {k: tuple(v.shape) for k, v in a.items()} == {k: tuple(v.shape) for k, v in b.items()}
-        assert list(syn.state_dict_spec(cfg)) == list(a.keys())
+def test_state_dict_equals_reference_layout():
+    """The reference's own state-dict layout (tests/golden/reference.npz, make_golden.py reference)."""
+    for name in ("h4", "favor"):                          # favor_relu: + the projection_matrix buffers
+        layout, kw = reference_state_dict_layout(name)
+        cfg = syn.make_config(**kw)
+        b = SuperGlue(cfg).state_dict()
+        assert [k for k, _ in layout] == list(b.keys())   # same names in the same registration order
+        assert dict(layout) == {k: tuple(v.shape) for k, v in b.items()}
+        assert list(syn.state_dict_spec(cfg)) == [k for k, _ in layout]
 
 
 @pytest.mark.parametrize("name", ["c1", "flags", "nodesc", "mid", "siren", "linear", "favor"])
@@ -210,6 +209,32 @@ def test_pack_survives_trained_checkpoint_statistics():
         model.linear_proj.weight[3, 3, 0] = float("nan")
     with pytest.raises(RuntimeError, match="OG_E_RANGE"):
         model.pack_host()
+
+
+def test_bench_dump_outputs_is_bounded_exact_and_repeatable(monkeypatch, tmp_path):
+    """bench.py --dump-outputs: every array the timed step returned, float32 / float64, all files under the size cap; arrays that fit are
+    stored whole and exact, larger ones as the same seeded sample of their elements in every run; the ragged path's per-pair list is named by pair."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 200_000)
+    g = torch.Generator().manual_seed(0)
+    out = {"scores": torch.randn(2, 201, 221, generator=g), "matches0": torch.randint(-1, 220, (2, 200), generator=g),
+           "matching_scores0": torch.rand(2, 200, generator=g)}
+    for d in ("a", "b"):
+        bench.dump_outputs(out, str(tmp_path / d))
+    assert sorted(f.name for f in (tmp_path / "a").iterdir()) == ["matches0.npy", "matching_scores0.npy", "scores.npy"]
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 200_000
+    plan = {k: draws for k, _, draws in bench._dump_plan(out)}
+    assert plan["matches0"] is None and plan["matching_scores0"] is None and plan["scores"] is not None
+    for name, t in out.items():
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == (np.float32 if t.is_floating_point() else np.float64) and np.array_equal(a, b)
+        if plan[name] is None:
+            assert np.array_equal(a, t.numpy().astype(a.dtype))
+        else:
+            pos = np.unique(np.random.default_rng(bench.DUMP_SEED).integers(0, t.numel(), size=plan[name]))
+            assert len(pos) > plan[name] // 2 and np.array_equal(a, t.reshape(-1).numpy()[pos])
+    bench.dump_outputs([{"scores": torch.zeros(3, 4)}, {"scores": torch.ones(2, 2)}], str(tmp_path / "ragged"))
+    assert np.array_equal(np.load(tmp_path / "ragged" / "pair001_scores.npy"), np.ones((2, 2), np.float32))
 
 
 def test_bench_self_spawns_one_process_per_gpu():

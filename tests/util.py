@@ -29,6 +29,17 @@ def load_case(name):
     return z, cfg, sd, data
 
 
+def load_reference():
+    """tests/golden/reference.npz: the reference's outputs on two small cases and its state-dict layouts (make_golden.py reference)."""
+    return dict(np.load(os.path.join(GOLDEN, "reference.npz"), allow_pickle=False))
+
+
+def reference_state_dict_layout(name):
+    """-> ([(name, shape), ...] of the reference's state dict in registration order, config kwargs) for the layout case `name`."""
+    z = load_reference()
+    return ast.literal_eval(str(z[f"layout_{name}/state_dict"])), ast.literal_eval(str(z[f"layout_{name}/config_kwargs"]))
+
+
 def to_device(data, device):
     return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in data.items()}
 
