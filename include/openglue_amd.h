@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OG_ABI_VERSION 10
+#define OG_ABI_VERSION 11
 
 #define OG_E_INVALID   (-1)  /* NULL pointer / non-positive size                         */
 #define OG_E_SHAPE     (-2)  /* unsupported shape (see og_check_shape)                   */
@@ -475,6 +475,58 @@ int og_compact_matches(const int64_t* matches0, const float* matching_scores0, c
                        int32_t batch, int32_t m, int32_t n, int64_t* matching_idxs, int64_t* batch_indexes,
                        float* confidence, float* mlafs0, float* mlafs1, float* keypoints0, float* keypoints1,
                        int32_t* count_dev, void* workspace_dev, void* stream);
+
+/* ---- the training step's supervision: labels before the matcher, the loss after it (matching_module.py:83-105) ---- */
+
+/* models/gt_matches_generation.py generate_gt_matches with utils/misc.py:21-103: ground-truth labels from keypoints0 [B][m][2],
+ * keypoints1 [B][n][2] (pixels, 8-byte aligned) and a known transformation.
+ * transform 0 'perspective': H [B][3][3] maps image 0 to image 1 (the reverse direction uses its inverse).
+ * transform 1 '3d_reprojection': K0, K1, R [B][3][3], T [B][3]; depth0 / depth1 either per keypoint ([B][m], [B][n]: depth*_h = 0)
+ *   or a depth map [B][depth*_h][depth*_w] read at the keypoint truncated to int64 (torch indexing: [-size, 0) wraps around).
+ *   A depth of |d| <= 1e-8 (torch.isclose against 0) marks the keypoint invalid.
+ * Reprojection ([x, y, 1] through the matrices, divided by w + 1e-8; 3x3 inverses by the adjugate), all-pairs nearest neighbours
+ * and labels are computed in fp64 without forming any B x m x n matrix.  gt_matches0 [B][m], gt_matches1 [B][n] (int64):
+ *   apply_thresholds = 0 (what the reference produces -- its threshold writes land on copies):
+ *     gt0[i] = nn0[i] if nn1[nn0[i]] == i else -1;  -2 where keypoint i has no depth;  image 1 likewise.
+ *   apply_thresholds = 1 (the rules of gt_matches_generation.py:63-68, as in-place writes in source order): a mutual pair whose
+ *     symmetric distance 0.5 (d0[i] + d1[nn0[i]]) exceeds positive_threshold is -2, exceeds negative_threshold is -1; a
+ *     non-mutual keypoint within negative_threshold of its neighbour is -2; no depth -2; a mutual keypoint whose neighbour
+ *     has no depth -2.
+ * status_dev: one int32 the call zeroes and sets to bit 0 / bit 1 when a depth-map index of image 0 / image 1 is out of range
+ *   (the reference raises IndexError; here the depth is not read and counts as missing).  Read it after the stream completes.
+ * workspace: og_gt_matches_workspace_bytes, 16-byte aligned.  Returns OG_E_FLAG for an unknown transform. */
+size_t og_gt_matches_workspace_bytes(int32_t batch, int32_t m, int32_t n);
+int og_gt_matches(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1, int32_t transform,
+                  const float* H, const float* K0, const float* K1, const float* R, const float* T,
+                  const float* depth0, int32_t depth0_h, int32_t depth0_w, const float* depth1, int32_t depth1_h, int32_t depth1_w,
+                  int32_t apply_thresholds, double positive_threshold, double negative_threshold,
+                  int64_t* gt_matches0, int64_t* gt_matches1, int32_t* status_dev, void* workspace_dev, void* stream);
+
+/* utils/losses.py criterion.  scores [B][m+1][n+1] (log-assignment with dustbins), gt_matches0 [B][m], gt_matches1 [B][n] (int64:
+ * j >= 0 matched, -1 unmatched, anything else ignored).  losses[0] = the NLL 'loss': per pair the mean of -scores over the
+ * matched entries + 0.5 (mean over unmatched0 at the dustbin column + mean over unmatched1 at the dustbin row), an empty set
+ * contributing 0, summed over pairs in order and divided by B.  with_margin != 0: losses[1] = 'metric_loss' on the channel-first
+ * context_descriptors0 [B][D][m] / 1 [B][D][n] (read in place): dist = 0.5 (1 - a^.b^) on the F.normalize'd columns (exact-fp32
+ * MFMA Gram matrix, no B x m x n buffer), triplet terms max(0, d_ap - d_an + margin) against the closest non-positive in the row
+ * and in the column of each matched pair, hinge terms max(0, margin - d_an) for the unmatched keypoints of either image, averaged
+ * per pair like the NLL; with_margin = 0: losses[1] = 0 and the descriptors are not read (may be NULL).  Both values are
+ * bit-identical from run to run.  workspace: og_criterion_workspace_bytes (same with_margin), 16-byte aligned; it carries what
+ * og_criterion_backward needs, so keep it until then. */
+size_t og_criterion_workspace_bytes(int32_t batch, int32_t m, int32_t n, int32_t with_margin);
+int og_criterion_forward(const float* scores, const int64_t* gt_matches0, const int64_t* gt_matches1,
+                         const float* context_descriptors0, const float* context_descriptors1,
+                         int32_t batch, int32_t m, int32_t n, int32_t D, int32_t with_margin, float margin,
+                         float* losses, void* workspace_dev, void* stream);
+/* Gradients of grad_losses[0] * loss + grad_losses[1] * metric_loss (grad_losses: device [2], NULL = both 1), with the inputs
+ * and the workspace of the forward call.  grad_scores [B][m+1][n+1] (NULL: skipped) is written densely: zero except
+ * -w / B at the labelled entries and -0.5 w / B at the dustbin entries (w = 1 / set size).  grad_context_descriptors0/1
+ * ([B][D][m], [B][D][n]; both or neither, with_margin only) are written in full; their O(m + n) scattered contributions are
+ * float atomics, so they may differ in the last bits from run to run. */
+int og_criterion_backward(const int64_t* gt_matches0, const int64_t* gt_matches1,
+                          const float* context_descriptors0, const float* context_descriptors1,
+                          int32_t batch, int32_t m, int32_t n, int32_t D, int32_t with_margin, float margin,
+                          const float* grad_losses, const void* workspace_dev, float* grad_scores,
+                          float* grad_context_descriptors0, float* grad_context_descriptors1, void* stream);
 
 #ifdef __cplusplus
 }
