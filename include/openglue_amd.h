@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OG_ABI_VERSION 11
+#define OG_ABI_VERSION 12
 
 #define OG_E_INVALID   (-1)  /* NULL pointer / non-positive size                         */
 #define OG_E_SHAPE     (-2)  /* unsupported shape (see og_check_shape)                   */
@@ -527,6 +527,38 @@ int og_criterion_backward(const int64_t* gt_matches0, const int64_t* gt_matches1
                           int32_t batch, int32_t m, int32_t n, int32_t D, int32_t with_margin, float margin,
                           const float* grad_losses, const void* workspace_dev, float* grad_scores,
                           float* grad_context_descriptors0, float* grad_context_descriptors1, void* stream);
+
+/* ABI v12 -- utils/metrics.py, the validation metrics (models/matching_module.py:107-131).  Pairs in the layout SuperGlue.match
+ * returns: keypoints0 [B][m][2], keypoints1 [B][n][2] (fp32 pixels, 8-byte aligned), matches0 [B][m] (int64; a keypoint i is
+ * matched when i < num_keypoints0[b] and 0 <= matches0[i] < n), num_keypoints0 [B] int32 (NULL: m), K0, K1, R [B][3][3] and
+ * T [B][3] (fp32; camera 0 at the identity).  No entry synchronises with the host; each launches a fixed number of kernels.
+ *
+ * og_epipolar_precision: AccuracyUsingEpipolarDist.  Calibrated points (x - c) / f, E = [T]x R, the squared symmetric epipolar
+ *   distance (x1^T E x0)^2 (1 / ((E x0)_0^2 + (E x0)_1^2) + 1 / ((E^T x1)_0^2 + (E^T x1)_1^2)) in fp64; a match is correct when
+ *   it is < threshold.  precision = correct / matched, matching_score = correct / num_keypoints0 (both 0 without matches),
+ *   num_correct [B].  One kernel. */
+int og_epipolar_precision(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                          const int64_t* matches0, const int32_t* num_keypoints0, const float* K0, const float* K1,
+                          const float* R, const float* T, double threshold, float* precision, float* matching_score,
+                          int32_t* num_correct, void* stream);
+/* og_essential_5pt: the five-point minimal solver (Nister / Stewenius), fp64.  x0, x1 [count][5][2] calibrated correspondences
+ *   (x1^T E x0 = 0) -> E [count][10][9] (row-major, unit Frobenius norm; the slots past num_solutions[p] are scratch) and
+ *   num_solutions [count] int32 (0..10).  Two kernels; E doubles as their scratch, so no workspace. */
+int og_essential_5pt(int32_t count, const double* x0, const double* x1, double* E, int32_t* num_solutions, void* stream);
+/* og_relative_pose: CameraPoseAUC's pose.  RANSAC over the five-point solver in calibrated space: `hypotheses` samples of 5
+ *   distinct matches drawn by a counter-based hash of (seed, pair_offset + b, hypothesis), every solution scored by the squared
+ *   Sampson error <= thr^2, thr = 2 ransac_threshold / mean(K0[0][0] + K1[0][0], K0[1][1] + K1[1][1]) (fp32); the model with
+ *   the most inliers wins, the lowest (hypothesis, solution) on ties, so every output is identical from run to run.  Then
+ *   kornia's cheirality choice among (R1, t), (R1, -t), (R2, t), (R2, -t) over the inliers, and the error against (R, T):
+ *   error [B] = max(rotation error, translation error) in degrees (inf with fewer than 5 matches or no model), R_pred [B][3][3],
+ *   t_pred [B][3] (unit; zeros without a model), inliers [B][m] uint8, num_inliers [B] int32.  workspace:
+ *   og_relative_pose_workspace_bytes, 16-byte aligned.  10 hypotheses <= 2^30 and batch * hypotheses <= 2^30.  Five kernels. */
+size_t og_relative_pose_workspace_bytes(int32_t batch, int32_t m, int32_t hypotheses);
+int og_relative_pose(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                     const int64_t* matches0, const int32_t* num_keypoints0, const float* K0, const float* K1,
+                     const float* R, const float* T, float ransac_threshold, int32_t hypotheses, uint64_t seed,
+                     int64_t pair_offset, float* error, float* R_pred, float* t_pred, uint8_t* inliers,
+                     int32_t* num_inliers, void* workspace_dev, void* stream);
 
 #ifdef __cplusplus
 }
