@@ -37,6 +37,7 @@ def _hipcc() -> str:
 # live on packed fp32, keep it).  The host pass does not know the feature and says so; harmless.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 PER_FILE_FLAGS = {"attention.hip": _NO_PACKED_FP32}
+FLAGS = ["--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-O3", "-Wall", "-Wno-unused-function"]      # every source; PER_FILE_FLAGS add to these
 
 
 def _stale(target: str, deps) -> bool:
@@ -50,7 +51,7 @@ def build(force: bool = False, debug: bool = False, verbose: bool = True) -> str
     os.makedirs(LIB_DIR, exist_ok=True)
     hipcc = _hipcc()
     headers = [os.path.join(CSRC, "og_common.h"), os.path.join(os.path.dirname(HERE), "include", "openglue_amd.h")]
-    flags = ["--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-O3", "-Wall", "-Wno-unused-function"]
+    flags = list(FLAGS)
     if debug:
         flags += ["-g", "-save-temps=obj"]
     objs, jobs = [], []

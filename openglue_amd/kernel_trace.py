@@ -1,0 +1,60 @@
+"""Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py) and the
+form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
+their own.
+
+launched_kernels(fn) runs fn() under torch.profiler (ProfilerActivity.CUDA: on ROCm, kineto's roctracer records every dispatched kernel
+by its demangled name, the library's own included), synchronises, and returns the names in launch order, shortened to the template:
+`void (anonymous namespace)::attention_dma_kernel<64, RaggedNone, 2, 1, 0, 0>(AttnArgs, RaggedNone)` ->
+`attention_dma_kernel<64, RaggedNone, 2, 1, 0, 0>`.  A window in which the profiler saw no device kernel at all is an error, not an
+empty list: an assertion over the names would then hold vacuously.
+"""
+import re
+
+import torch
+
+ATTENTION_FORWARD = ("attention_kernel<", "attention_dma_kernel<", "attention_p16_kernel<")
+
+
+def short_name(name: str) -> str:
+    """Demangled kernel name -> `kernel<template args>` without return type, namespaces and argument list."""
+    if name.startswith("_Z"):          # a tracer that reports mangled names
+        import subprocess
+        try:
+            name = subprocess.run(["c++filt", name], capture_output=True, text=True, check=True).stdout.strip() or name
+        except (OSError, subprocess.CalledProcessError):
+            pass
+    s = name.replace("(anonymous namespace)::", "").strip()
+    if s.startswith("void "):
+        s = s[5:]
+    depth = 0
+    for i, c in enumerate(s):          # the argument list is the first '(' outside the template brackets
+        if c == "<":
+            depth += 1
+        elif c == ">":
+            depth -= 1
+        elif c == "(" and depth == 0:
+            s = s[:i]
+            break
+    s = s.strip()
+    j = s.find("<")
+    head = s if j < 0 else s[:j]
+    return head.split("::")[-1] + ("" if j < 0 else s[j:])
+
+
+def launched_kernels(fn) -> list:
+    """Run fn() and return the shortened names of the device kernels it launched, in launch order."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    evs = [e for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+    if not evs:
+        raise RuntimeError("kernel_trace: the profiler recorded no device kernel in this window -- cannot tell which kernels ran")
+    evs.sort(key=lambda e: e.time_range.start)
+    return [short_name(e.name) for e in evs if not re.match(r"^(Memcpy|Memset|hipMem)", e.name)]
+
+
+def attention_instances(names) -> set:
+    """The attention forward instances among `names`."""
+    return {n for n in names if n.startswith(ATTENTION_FORWARD)}
