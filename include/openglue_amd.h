@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OG_ABI_VERSION 12
+#define OG_ABI_VERSION 13
 
 #define OG_E_INVALID   (-1)  /* NULL pointer / non-positive size                         */
 #define OG_E_SHAPE     (-2)  /* unsupported shape (see og_check_shape)                   */
@@ -559,6 +559,37 @@ int og_relative_pose(int32_t batch, int32_t m, int32_t n, const float* keypoints
                      const float* R, const float* T, float ransac_threshold, int32_t hypotheses, uint64_t seed,
                      int64_t pair_offset, float* error, float* R_pred, float* t_pred, uint8_t* inliers,
                      int32_t* num_inliers, void* workspace_dev, void* stream);
+
+/* ABI v13 -- the SuperPoint detector / descriptor (models/features/superpoint/model.py, SuperPointNet / SuperPointNetBn), inference
+ * only (eval-mode BatchNorm, folded at pack time).  descriptor_dim 256.  Image [B][H][W] fp32, H, W >= 8, B * H * W <= 2^26;
+ * Hc = H / 8, Wc = W / 8 (floor, as the three 2x2 max-pools), the heatmap is [B][8 Hc][8 Wc].
+ *
+ * og_superpoint_pack (host): params = 24 host pointers, weight [out][in][3][3 or 1] and bias of conv1a, conv1b, conv2a, conv2b,
+ *   conv3a, conv3b, conv4a, conv4b, convPa, convPb, convDa, convDb; with batch_norm != 0 followed by 48 more, weight / bias /
+ *   running_mean / running_var of bn1a, bn1b, ..., bn4b, bnPa, bnPb, bnDa, bnDb (BatchNorm eps bn_eps).  Writes
+ *   og_superpoint_packed_bytes bytes; OG_E_RANGE if a folded weight is not finite.
+ * og_superpoint_dense: image -> heatmap [B][8 Hc][8 Wc] (softmax over 65, dustbin dropped, depth-to-space) and coarse descriptors
+ *   [B][Hc][Wc][256] (NHWC, divided by their L2 norm).  Workspace og_superpoint_workspace_bytes, 16-byte aligned; shared with
+ *   og_superpoint_detect (the two run one after the other on the stream).
+ * og_superpoint_detect: heatmap [B][Hh][Wh] -> NMS (kornia nms2d: replicate padding, strictly greater than the other k*k-1),
+ *   > threshold and != 0, remove_borders, top_k_keypoints(max_kpts, -1 = all) and min_stack.  nms_kernel odd, 3..17.
+ *   counts[b] = candidates of image b, counts[B + b] = keypoints kept (equal for every b).  sel_idx / sel_score [B][sel_ld]
+ *   (sel_ld >= og_superpoint_capacity) receive raster index y * Wh + x and score of each kept keypoint: in raster order when
+ *   neither top-k nor min_stack cut (every image keeps the same count, uncut), otherwise by descending score, equal scores
+ *   in raster order.
+ * og_superpoint_describe: n = counts[B] keypoints per image -> lafs [B][n][2][3] (identity, (x, y)), scores [B][n], descriptors
+ *   [B][n][256] (sample_desc_from_points: bilinear, align_corners=False, zero padding, then F.normalize). */
+size_t og_superpoint_packed_bytes(int32_t descriptor_dim);
+int og_superpoint_pack(int32_t descriptor_dim, int32_t batch_norm, float bn_eps, const float* const* params, void* packed_host);
+int og_superpoint_capacity(int32_t H, int32_t W, int32_t max_kpts);
+size_t og_superpoint_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t nms_kernel, int32_t max_kpts);
+int og_superpoint_dense(int32_t batch, int32_t H, int32_t W, const float* image, const void* packed_dev, float* heatmap,
+                        float* coarse_desc, void* workspace_dev, void* stream);
+int og_superpoint_detect(int32_t batch, int32_t Hh, int32_t Wh, int32_t nms_kernel, int32_t border, float threshold, int32_t max_kpts,
+                         const float* heatmap, int32_t* counts, int32_t* sel_idx, float* sel_score, int64_t sel_ld,
+                         void* workspace_dev, void* stream);
+int og_superpoint_describe(int32_t batch, int32_t Hc, int32_t Wc, int32_t n, const int32_t* sel_idx, const float* sel_score,
+                           int64_t sel_ld, const float* coarse_desc, float* lafs, float* scores, float* descriptors, void* stream);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from typing import Optional
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OPENGLUE_AMD_LIB") or os.path.join(HERE, "lib", "libopenglue_amd.so")   # override: A/B builds
 
-OG_ABI_VERSION = 12
+OG_ABI_VERSION = 13
 OG_FLAG_RESIDUAL, OG_FLAG_USE_OFFSET, OG_FLAG_NO_DESCRIPTORS, OG_FLAG_SIREN_ENCODER, OG_FLAG_LINEAR_ATTENTION = 1, 2, 4, 8, 16
 OG_FLAG_FAVOR_RELU = 32
 OG_MAX_HIDDEN = 8
@@ -152,6 +152,13 @@ SYMBOLS = {
     "og_relative_pose_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "og_relative_pose": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i32, C.c_uint64, _i64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_superpoint_packed_bytes": (_sz, [_i32]),
+    "og_superpoint_pack": (C.c_int, [_i32, _i32, _f, _vp, _vp]),
+    "og_superpoint_capacity": (C.c_int, [_i32, _i32, _i32]),
+    "og_superpoint_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "og_superpoint_dense": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_superpoint_detect": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _f, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "og_superpoint_describe": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,687 @@
+// SuperPoint detector + descriptor, inference only (reference models/features/superpoint/model.py, superpoint/utils.py,
+// models/features/utils.py:26-51 min_stack).  Exact fp32 throughout: the convolutions run on v_mfma_f32_32x32x2_f32, the
+// selection is a pure comparison of fp32 heatmap values, so the path is deterministic.
+//
+// Layout: activations NHWC fp32.  Stages (og_superpoint_dense / _detect / _describe, include/openglue_amd.h):
+//   conv1a       1 -> 64, VALU, one thread per (pixel, 4 channels)                                  full resolution
+//   conv3x3      implicit GEMM: a workgroup owns 8 x 16 output pixels x BN channels; the input tile and its 1-pixel halo
+//                are staged in LDS 32 channels at a time, the K loop runs over 9 taps x 32 channels reading A fragments at
+//                tap offsets (no im2col buffer); weights are packed fragment-major with BatchNorm folded.  Epilogue: bias,
+//                ReLU and, for conv{1,2,3}b, the 2x2 max-pool (floor semantics), so the unpooled map is never stored.
+//                convPa and convDa run as one launch with 512 output channels.
+//   cell         convPb (65) and convDb (D) on the 512-channel hidden map: softmax over 65, dustbin dropped, depth-to-space
+//                into the heatmap [B][Hc*8][Wc*8]; descriptor divided by its L2 norm (no eps) into [B][Hc][Wc][D].
+//   nms          kornia nms2d restated: replicate padding by (k-1)/2, a pixel is kept only when STRICTLY greater than the
+//                maximum of its k*k-1 neighbours (centre excluded); plus F.threshold (> thr, != 0) and remove_borders.
+//                Per (row, 256-column segment) counts, an exclusive scan per image, then compaction in raster order.
+//   select       top_k_keypoints + min_stack on device: each candidate's rank under the key (score desc, raster index asc)
+//                is counted exactly, so the selection is identical from run to run and ties go to the lower raster index.
+//   describe     sample_desc_from_points (grid_sample bilinear, align_corners=False, zero padding) + F.normalize, LAFs, scores.
+#include "og_common.h"
+#include <cmath>
+
+namespace {
+
+constexpr int SP_TH = 8, SP_TW = 16;                 // conv output tile (pre-pool pixels)
+constexpr int SP_HALO_H = SP_TH + 2, SP_HALO_W = SP_TW + 2;
+constexpr int SP_KC = 32;                            // input channels staged per pass
+constexpr int SP_LDSC = SP_KC + 4;                   // padded pixel row in LDS: 16 consecutive pixels hit 16 distinct 4-bank slots
+constexpr int SP_NMS_SEG = 256;                      // columns per NMS segment
+constexpr int SP_NMS_RMAX = 8;                       // nms_kernel <= 17
+constexpr int SP_CELL_PIX = 32;                      // pixels per cell workgroup
+constexpr int SP_CELL_LD = 516;                      // hidden row in LDS (512 + 4)
+constexpr int SP_P_TILES = 3, SP_D_TILES = 8;        // convPb: 65 rows padded to 96; convDb: 256
+constexpr int SP_D = 256;
+
+struct SpLayout {
+    int64_t w1a, b1a;            // conv1a [9][64], [64]
+    int64_t w[8], b[8];          // conv1b, 2a, 2b, 3a, 3b, 4a, 4b, heads (Pa | Da): fragment-major, [Cout]
+    int64_t wc, bc;              // cell: [11 tiles][32 steps][64][4]; bias [96 | 256]
+    int64_t total;
+};
+constexpr int kCin[8] = {64, 64, 64, 64, 128, 128, 128, 128};
+constexpr int kCout[8] = {64, 64, 64, 128, 128, 128, 128, 512};
+
+SpLayout sp_layout() {
+    SpLayout L{};
+    int64_t o = 0;
+    L.w1a = o; o += 9 * 64;
+    L.b1a = o; o += 64;
+    for (int i = 0; i < 8; ++i) {
+        L.w[i] = o; o += (int64_t)kCout[i] * 9 * kCin[i];
+        L.b[i] = o; o += kCout[i];
+    }
+    L.wc = o; o += (int64_t)(SP_P_TILES + SP_D_TILES) * 32 * 256;
+    L.bc = o; o += 32 * SP_P_TILES + SP_D;
+    L.total = o;
+    return L;
+}
+
+// ---------------------------------------------------------------- conv1a (Cin = 1): VALU
+__global__ __launch_bounds__(256) void sp_conv1a_kernel(const float* __restrict__ img, const float* __restrict__ w,
+                                                        const float* __restrict__ bias, int B, int H, int W, float* __restrict__ out) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t total = (int64_t)B * H * W * 16;
+    if (t >= total) return;
+    const int c4 = (int)(t & 15) * 4;
+    const int64_t p = t >> 4;
+    const int x = (int)(p % W), y = (int)((p / W) % H);
+    const int64_t b = p / ((int64_t)W * H);
+    const float* im = img + b * H * W;
+    f32x4 acc = *reinterpret_cast<const f32x4*>(bias + c4);
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+            const int yy = y + ky - 1, xx = x + kx - 1;
+            const float v = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? im[(int64_t)yy * W + xx] : 0.f;
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(w + (ky * 3 + kx) * 64 + c4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = fmaf(wv[e], v, acc[e]);
+        }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc[e] = fmaxf(acc[e], 0.f);
+    *reinterpret_cast<f32x4*>(out + p * 64 + c4) = acc;
+}
+
+// ---------------------------------------------------------------- 3x3 convolution, implicit GEMM on fp32 MFMA
+// M = 128 output pixels (8 rows x 16 columns), N = BN channels, K = 9 taps x Cin.  4 waves as 2 x 2: wave (wm, wn) owns tile rows
+// 4 wm .. 4 wm + 3 (two 32-pixel MFMA tiles of two image rows each) and channels wn * BN/2 ..  A 32x32x2 MFMA tile row m is pixel
+// (row m >> 4, column m & 15) of its two-row band, so lane l's accumulator registers r, r+1, r+8, r+9 (r in {0, 2, 4, 6}) are the
+// four pixels of one 2x2 pooling window (mfma32_row): the pool is a register max.
+// Packed weights, per 32-channel output tile jt: [jt][step][lane][4] with step = (chunk * 9 + tap) * 4 + kk and
+// lane l holding W[co = 32 jt + (l & 31)][ci = 32 chunk + 8 kk + 4 (l >> 5) + e][tap] -- one coalesced 1 KiB read per fragment.
+template <int BN, bool POOL>
+__global__ __launch_bounds__(256, 2) void sp_conv3x3_kernel(const float* __restrict__ in, const float* __restrict__ wp,
+                                                            const float* __restrict__ bias, int B, int H, int W, int Cin, int Cout,
+                                                            float* __restrict__ out) {
+    constexpr int TM = 2, TN = BN / 64;
+    __shared__ __attribute__((aligned(16))) float tile[SP_HALO_H * SP_HALO_W * SP_LDSC];
+    const int tiles_x = (W + SP_TW - 1) / SP_TW, tiles_y = (H + SP_TH - 1) / SP_TH;
+    int id = blockIdx.x;
+    const int tx0 = (id % tiles_x) * SP_TW;
+    id /= tiles_x;
+    const int ty0 = (id % tiles_y) * SP_TH;
+    const int b = id / tiles_y;
+    const int n0 = blockIdx.y * BN;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int nsteps = 9 * Cin / 8;
+    const float* inb = in + (int64_t)b * H * W * Cin;
+
+    const float* wbase[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) wbase[j] = wp + ((int64_t)((n0 + wn * (BN / 2)) / 32 + j) * nsteps) * 256 + lane * 4;
+
+    f32x16 acc[TM][TN];
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    // the lane's A pixel in each of its M tiles, as an LDS offset at tap (0, 0) of the halo tile
+    int a_off[TM];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int m = lane & 31;
+        const int ry = 4 * wm + 2 * i + (m >> 4), rx = m & 15;
+        a_off[i] = (ry * SP_HALO_W + rx) * SP_LDSC + 4 * (lane >> 5);
+    }
+
+    f32x4 bcur[TN], bnext[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j) bcur[j] = *reinterpret_cast<const f32x4*>(wbase[j]);
+    int s = 0;
+    for (int c0 = 0; c0 < Cin; c0 += SP_KC) {
+        __syncthreads();
+        for (int f = tid; f < SP_HALO_H * SP_HALO_W * (SP_KC / 4); f += 256) {
+            const int q = f & 7, p = f >> 3;
+            const int py = p / SP_HALO_W, px = p - py * SP_HALO_W;
+            const int gy = ty0 - 1 + py, gx = tx0 - 1 + px;
+            f32x4 v{0.f, 0.f, 0.f, 0.f};
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = *reinterpret_cast<const f32x4*>(inb + ((int64_t)gy * W + gx) * Cin + c0 + q * 4);
+            *reinterpret_cast<f32x4*>(&tile[p * SP_LDSC + q * 4]) = v;
+        }
+        __syncthreads();
+        for (int tap = 0; tap < 9; ++tap) {
+            const int toff = ((tap / 3) * SP_HALO_W + (tap % 3)) * SP_LDSC;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk, ++s) {
+                if (s + 1 < nsteps) {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) bnext[j] = *reinterpret_cast<const f32x4*>(wbase[j] + (int64_t)(s + 1) * 256);
+                }
+                f32x4 a[TM];
+#pragma unroll
+                for (int i = 0; i < TM; ++i) a[i] = *reinterpret_cast<const f32x4*>(&tile[a_off[i] + toff + kk * 8]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int i = 0; i < TM; ++i)
+#pragma unroll
+                        for (int j = 0; j < TN; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], bcur[j][e], acc[i][j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < TN; ++j) bcur[j] = bnext[j];
+            }
+        }
+    }
+
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+        const int co = n0 + wn * (BN / 2) + j * 32 + (lane & 31);
+        const float bv = bias[co];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            const int band = ty0 + 4 * wm + 2 * i;              // first image row of this MFMA tile
+            if constexpr (POOL) {
+                const int Hp = H / 2, Wp = W / 2;
+                const int py = band / 2;
+                if (py >= Hp) continue;
+#pragma unroll
+                for (int r = 0; r < 8; r += 2) {
+                    const int m = mfma32_row(r, lane);           // even column, upper row of the window
+                    const int px = (tx0 + (m & 15)) / 2;
+                    if (px >= Wp) continue;
+                    float v = fmaxf(fmaxf(acc[i][j][r], acc[i][j][r + 1]), fmaxf(acc[i][j][r + 8], acc[i][j][r + 9]));
+                    v = fmaxf(v + bv, 0.f);
+                    out[(((int64_t)b * Hp + py) * Wp + px) * Cout + co] = v;
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = mfma32_row(r, lane);
+                    const int y = band + (m >> 4), x = tx0 + (m & 15);
+                    if (y >= H || x >= W) continue;
+                    out[(((int64_t)b * H + y) * W + x) * Cout + co] = fmaxf(acc[i][j][r] + bv, 0.f);
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- cell: convPb + softmax + depth-to-space, convDb + L2 norm
+// 32 pixels per workgroup; their 512 hidden channels sit in LDS.  11 output tiles of 32 (3 for the 65 logits, zero-padded to 96;
+// 8 for the 256 descriptor channels), wave w takes tiles w, w + 4, w + 8.  The tiles' results go back to LDS, then one thread per
+// pixel reduces (max / sum of exp over 65, sum of squares over 256) and all threads write the outputs coalesced.
+__global__ __launch_bounds__(256, 1) void sp_cell_kernel(const float* __restrict__ hidden, const float* __restrict__ wc,
+                                                         const float* __restrict__ bc, int npix, int Hc, int Wc,
+                                                         float* __restrict__ heat, float* __restrict__ desc) {
+    constexpr int LD_P = 97, LD_D = SP_D + 4;
+    __shared__ __attribute__((aligned(16))) float lds[SP_CELL_PIX * SP_CELL_LD];
+    __shared__ float stat[SP_CELL_PIX][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t p0 = (int64_t)blockIdx.x * SP_CELL_PIX;
+    for (int f = tid; f < SP_CELL_PIX * 128; f += 256) {
+        const int r = f >> 7, q = f & 127;
+        f32x4 v{0.f, 0.f, 0.f, 0.f};
+        if (p0 + r < npix) v = *reinterpret_cast<const f32x4*>(hidden + (p0 + r) * 512 + q * 4);
+        *reinterpret_cast<f32x4*>(&lds[r * SP_CELL_LD + q * 4]) = v;
+    }
+    __syncthreads();
+    f32x16 acc[3];
+    int tiles[3], nt = 0;
+    for (int t = wave; t < SP_P_TILES + SP_D_TILES; t += 4) tiles[nt++] = t;
+#pragma unroll
+    for (int u = 0; u < 3; ++u)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[u][r] = 0.f;
+    const int a_row = (lane & 31) * SP_CELL_LD + 4 * (lane >> 5);
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+        if (u >= nt) break;
+        const int t = tiles[u];
+        const int kbase = t < SP_P_TILES ? 0 : 256;
+        const float* wt = wc + (int64_t)t * 32 * 256 + lane * 4;
+        f32x4 bcur = *reinterpret_cast<const f32x4*>(wt), bnext;
+        for (int s = 0; s < 32; ++s) {
+            if (s + 1 < 32) bnext = *reinterpret_cast<const f32x4*>(wt + (s + 1) * 256);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(&lds[a_row + kbase + s * 8]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], bcur[e], acc[u], 0, 0, 0);
+            bcur = bnext;
+        }
+    }
+    __syncthreads();                       // hidden no longer needed: the logits and descriptors reuse the LDS
+    float* lp = lds;                       // [32][LD_P]
+    float* ld = lds + SP_CELL_PIX * LD_P;  // [32][LD_D]
+#pragma unroll
+    for (int u = 0; u < 3; ++u) {
+        if (u >= nt) break;
+        const int t = tiles[u];
+        const int col = (t < SP_P_TILES ? t : t - SP_P_TILES) * 32 + (lane & 31);
+        const float bv = bc[(t < SP_P_TILES ? 0 : 32 * SP_P_TILES) + col];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = mfma32_row(r, lane);
+            if (t < SP_P_TILES) {
+                if (col < 65) lp[row * LD_P + col] = acc[u][r] + bv;
+            } else {
+                ld[row * LD_D + col] = acc[u][r] + bv;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid < SP_CELL_PIX) {
+        const float* l = lp + tid * LD_P;
+        float mx = l[0];
+        for (int c = 1; c < 65; ++c) mx = fmaxf(mx, l[c]);
+        float sum = 0.f;
+        for (int c = 0; c < 65; ++c) sum += expf(l[c] - mx);
+        stat[tid][0] = mx;
+        stat[tid][1] = sum;
+    } else if (tid >= 64 && tid < 64 + SP_CELL_PIX) {
+        const float* d = ld + (tid - 64) * LD_D;
+        float ss = 0.f;
+        for (int c = 0; c < SP_D; ++c) ss = fmaf(d[c], d[c], ss);
+        lp[(tid - 64) * LD_P + 96] = sqrtf(ss);             // slot 96 of the logit row is free (65 used)
+    }
+    __syncthreads();
+    const int Hh = Hc * 8, Wh = Wc * 8;
+    for (int f = tid; f < SP_CELL_PIX * 64; f += 256) {
+        const int r = f >> 6, c = f & 63;
+        const int64_t p = p0 + r;
+        if (p >= npix) continue;
+        const int64_t b = p / ((int64_t)Hc * Wc);
+        const int rem = (int)(p - b * Hc * Wc), cy = rem / Wc, cx = rem - cy * Wc;
+        heat[(b * Hh + cy * 8 + (c >> 3)) * Wh + cx * 8 + (c & 7)] = expf(lp[r * LD_P + c] - stat[r][0]) / stat[r][1];
+    }
+    for (int f = tid; f < SP_CELL_PIX * (SP_D / 4); f += 256) {
+        const int r = f / (SP_D / 4), c4 = (f % (SP_D / 4)) * 4;
+        const int64_t p = p0 + r;
+        if (p >= npix) continue;
+        const float nrm = lp[r * LD_P + 96];
+        f32x4 v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = ld[r * LD_D + c4 + e] / nrm;
+        *reinterpret_cast<f32x4*>(desc + p * SP_D + c4) = v;
+    }
+}
+
+// ---------------------------------------------------------------- NMS + threshold + borders, segment counts
+// Workgroup (segment, row, image): 256 columns of one heatmap row; LDS holds rows y - r .. y + r of columns x0 - r .. x0 + 255 + r,
+// coordinates clamped into the image (replicate padding).  mask[b][y][x] = 1 for a candidate; seg[b][y * nseg + s] = its count.
+__global__ __launch_bounds__(256) void sp_nms_kernel(const float* __restrict__ heat, int Hh, int Wh, int rad, int border, float thr,
+                                                     uint8_t* __restrict__ mask, int32_t* __restrict__ seg) {
+    __shared__ float t[2 * SP_NMS_RMAX + 1][SP_NMS_SEG + 2 * SP_NMS_RMAX];
+    const int nseg = (Wh + SP_NMS_SEG - 1) / SP_NMS_SEG;
+    const int s = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
+    const int x0 = s * SP_NMS_SEG, tid = threadIdx.x;
+    const float* hb = heat + (int64_t)b * Hh * Wh;
+    const int rows = 2 * rad + 1, cols = SP_NMS_SEG + 2 * rad;
+    for (int f = tid; f < rows * cols; f += 256) {
+        const int rr = f / cols, cc = f - rr * cols;
+        const int yy = min(max(y - rad + rr, 0), Hh - 1), xx = min(max(x0 - rad + cc, 0), Wh - 1);
+        t[rr][cc] = hb[(int64_t)yy * Wh + xx];
+    }
+    __syncthreads();
+    const int x = x0 + tid;
+    int keep = 0;
+    if (x < Wh) {
+        const float v = t[rad][tid + rad];
+        float mx = OG_NEG_INF;
+        for (int dy = 0; dy < rows; ++dy)
+            for (int dx = 0; dx < rows; ++dx)
+                if (dy != rad || dx != rad) mx = fmaxf(mx, t[dy][tid + dx]);
+        keep = v > mx && v > thr && v != 0.f && x >= border && x < Wh - border && y >= border && y < Hh - border;
+        mask[((int64_t)b * Hh + y) * Wh + x] = (uint8_t)keep;
+    }
+    const int cnt = __syncthreads_count(keep);
+    if (tid == 0) seg[((int64_t)b * Hh + y) * nseg + s] = cnt;
+}
+
+// exclusive scan of one image's segment counts (raster order), total -> counts[b]
+__global__ __launch_bounds__(256) void sp_scan_kernel(int32_t* __restrict__ seg, int nseg_img, int32_t* __restrict__ counts) {
+    __shared__ int32_t part[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int32_t* sb = seg + (int64_t)b * nseg_img;
+    const int per = (nseg_img + 255) / 256;
+    const int lo = min(tid * per, nseg_img), hi = min(lo + per, nseg_img);
+    int sum = 0;
+    for (int i = lo; i < hi; ++i) sum += sb[i];
+    part[tid] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        int run = 0;
+        for (int i = 0; i < 256; ++i) {
+            const int v = part[i];
+            part[i] = run;
+            run += v;
+        }
+        counts[b] = run;
+    }
+    __syncthreads();
+    int run = part[tid];
+    for (int i = lo; i < hi; ++i) {
+        const int v = sb[i];
+        sb[i] = run;
+        run += v;
+    }
+}
+
+// candidates of one segment written at its scanned offset, in column order: cand_idx = y * Wh + x, cand_score = heat
+__global__ __launch_bounds__(256) void sp_compact_kernel(const float* __restrict__ heat, const uint8_t* __restrict__ mask, int Hh, int Wh,
+                                                         const int32_t* __restrict__ seg, int64_t cap, int32_t* __restrict__ cidx,
+                                                         float* __restrict__ cscore) {
+    __shared__ int wsum[4];
+    const int nseg = (Wh + SP_NMS_SEG - 1) / SP_NMS_SEG;
+    const int s = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int x = s * SP_NMS_SEG + tid;
+    const int64_t pix = ((int64_t)b * Hh + y) * Wh + x;
+    const bool keep = x < Wh && mask[pix];
+    const uint64_t bal = __ballot(keep);
+    if (lane == 0) wsum[wave] = __popcll(bal);
+    __syncthreads();
+    if (!keep) return;
+    int off = seg[((int64_t)b * Hh + y) * nseg + s] + __popcll(bal & ((1ull << lane) - 1));
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    cidx[b * cap + off] = y * Wh + x;
+    cscore[b * cap + off] = heat[pix];
+}
+
+// top_k_keypoints + min_stack.  Per image: c_b = n_b if k < 0 or k >= n_b else k; m = min_b c_b.  If every c_b is equal each image
+// keeps c_b -- in raster order when it was not cut (c_b == n_b), else its c_b best by descending score; otherwise every image keeps
+// its m best by descending score (min_stack's torch.topk runs on every image, the smallest included).  The rank of candidate i is
+// the number of candidates j with (score_j, -index_j) > (score_i, -index_i): exact, distinct, independent of scheduling.
+__global__ __launch_bounds__(256) void sp_select_kernel(const int32_t* __restrict__ counts_in, int B, int max_kpts, int64_t cap,
+                                                        const int32_t* __restrict__ cidx, const float* __restrict__ cscore, int64_t sel_ld,
+                                                        int32_t* __restrict__ counts_out, int32_t* __restrict__ sidx, float* __restrict__ sscore) {
+    __shared__ float ss[256];
+    __shared__ int32_t si[256];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    int cmin = 0x7fffffff, cfirst = -1;
+    bool equal = true;
+    for (int i = 0; i < B; ++i) {
+        const int n = counts_in[i];
+        const int c = (max_kpts < 0 || max_kpts >= n) ? n : max_kpts;
+        if (cfirst < 0) cfirst = c;
+        equal = equal && c == cfirst;
+        cmin = min(cmin, c);
+    }
+    const int n = counts_in[b];
+    const int cb = (max_kpts < 0 || max_kpts >= n) ? n : max_kpts;
+    const int m = equal ? cb : cmin;
+    const bool raster = equal && cb == n;
+    if (blockIdx.x == 0 && tid == 0) {
+        counts_out[b] = n;
+        counts_out[B + b] = m;
+    }
+    const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+    if ((int64_t)blockIdx.x * 256 >= n) return;
+    const int32_t* ci = cidx + b * cap;
+    const float* cs = cscore + b * cap;
+    const bool live = i < n;
+    const float v = live ? cs[i] : 0.f;
+    const int32_t vi = live ? ci[i] : 0;
+    if (raster) {
+        if (live && i < m) {
+            sidx[b * sel_ld + i] = vi;
+            sscore[b * sel_ld + i] = v;
+        }
+        return;
+    }
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += 256) {
+        __syncthreads();
+        if (j0 + tid < n) {
+            ss[tid] = cs[j0 + tid];
+            si[tid] = ci[j0 + tid];
+        }
+        __syncthreads();
+        const int lim = min(256, n - j0);
+        for (int j = 0; j < lim; ++j) {
+            const float u = ss[j];
+            rank += (u > v) || (u == v && si[j] < vi);
+        }
+    }
+    if (live && rank < m) {
+        sidx[b * sel_ld + rank] = vi;
+        sscore[b * sel_ld + rank] = v;
+    }
+}
+
+// one wave per keypoint: LAF, score, bilinear descriptor (grid_sample, align_corners=False, zero padding) and F.normalize
+__global__ __launch_bounds__(256) void sp_describe_kernel(int B, int Hc, int Wc, int n, const int32_t* __restrict__ sidx,
+                                                          const float* __restrict__ sscore, int64_t sel_ld, const float* __restrict__ cdesc,
+                                                          float* __restrict__ lafs, float* __restrict__ scores, float* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+    if (k >= n) return;
+    const int Wh = Wc * 8, Hh = Hc * 8;
+    const int idx = sidx[b * sel_ld + k];
+    const float x = (float)(idx % Wh), y = (float)(idx / Wh);
+    const int64_t o = (int64_t)b * n + k;
+    if (lane == 0) {
+        float* L = lafs + o * 6;
+        L[0] = 1.f; L[1] = 0.f; L[2] = x;
+        L[3] = 0.f; L[4] = 1.f; L[5] = y;
+        scores[o] = sscore[b * sel_ld + k];
+    }
+    // sample_desc_from_points: (p - cell/2 + 0.5) / (size - cell/2 - 0.5) * 2 - 1, then grid_sample's unnormalisation
+    const float gx = (x - 4.f + 0.5f) / ((float)Wh - 4.5f) * 2.f - 1.f;
+    const float gy = (y - 4.f + 0.5f) / ((float)Hh - 4.5f) * 2.f - 1.f;
+    const float ix = ((gx + 1.f) * Wc - 1.f) / 2.f, iy = ((gy + 1.f) * Hc - 1.f) / 2.f;
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
+    const float w_nw = ((float)x1 - ix) * ((float)y1 - iy), w_ne = (ix - fx) * ((float)y1 - iy);
+    const float w_sw = ((float)x1 - ix) * (iy - fy), w_se = (ix - fx) * (iy - fy);
+    const float* db = cdesc + (int64_t)b * Hc * Wc * SP_D + lane * 4;
+    f32x4 v{0.f, 0.f, 0.f, 0.f};
+    auto tap = [&](int yy, int xx, float w) {
+        if (yy < 0 || yy >= Hc || xx < 0 || xx >= Wc) return;
+        const f32x4 d = *reinterpret_cast<const f32x4*>(db + ((int64_t)yy * Wc + xx) * SP_D);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = fmaf(d[e], w, v[e]);
+    };
+    tap(y0, x0, w_nw);
+    tap(y0, x1, w_ne);
+    tap(y1, x0, w_sw);
+    tap(y1, x1, w_se);
+    const float ss = wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+    const float nrm = fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = v[e] / nrm;
+    *reinterpret_cast<f32x4*>(out + o * SP_D + lane * 4) = v;
+}
+
+// ---------------------------------------------------------------- host side
+struct Dims {
+    int H2, W2, H4, W4, Hc, Wc;
+};
+Dims dims(int H, int W) { return {H / 2, W / 2, H / 4, W / 4, H / 8, W / 8}; }
+
+int64_t sp_capacity(int Hh, int Wh, int max_kpts) {
+    // a candidate is strictly greater than its 8 neighbours (nms_kernel >= 3): at most one per 2x2 block
+    const int64_t cap = (int64_t)((Hh + 1) / 2) * ((Wh + 1) / 2);
+    return max_kpts > 0 && max_kpts < cap ? max_kpts : cap;
+}
+
+struct DetectWs {
+    uint8_t* mask;
+    int32_t* seg;
+    int32_t* cand_idx;
+    float* cand_score;
+    int32_t* counts;
+    size_t bytes;
+};
+DetectWs detect_layout(void* base, int B, int Hh, int Wh) {
+    const int64_t cap = sp_capacity(Hh, Wh, -1);
+    const int nseg = (Wh + SP_NMS_SEG - 1) / SP_NMS_SEG;
+    char* p = (char*)base;
+    size_t o = 0;
+    DetectWs w{};
+    w.mask = (uint8_t*)(p + o); o += og_round_up((int64_t)B * Hh * Wh, 256);
+    w.seg = (int32_t*)(p + o); o += og_round_up((int64_t)B * Hh * nseg * 4, 256);
+    w.cand_idx = (int32_t*)(p + o); o += og_round_up((int64_t)B * cap * 4, 256);
+    w.cand_score = (float*)(p + o); o += og_round_up((int64_t)B * cap * 4, 256);
+    w.counts = (int32_t*)(p + o); o += og_round_up((int64_t)B * 4, 256);
+    w.bytes = o;
+    return w;
+}
+size_t dense_bytes(int B, int H, int W) {
+    const Dims d = dims(H, W);
+    return og_round_up((int64_t)B * H * W * 64 * 4, 256) + og_round_up((int64_t)B * d.H2 * d.W2 * 64 * 4, 256);
+}
+bool dense_shape_ok(int B, int H, int W) { return B > 0 && H >= 8 && W >= 8 && (int64_t)B * H * W <= (1ll << 26); }
+
+template <int BN, bool POOL>
+void conv(const float* in, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout, float* out, hipStream_t st) {
+    const int tiles = ((W + SP_TW - 1) / SP_TW) * ((H + SP_TH - 1) / SP_TH) * B;
+    hipLaunchKernelGGL((sp_conv3x3_kernel<BN, POOL>), dim3(tiles, Cout / BN), dim3(256), 0, st, in, w, bias, B, H, W, Cin, Cout, out);
+}
+
+double fold_scale(const float* const* bn, int c, double eps) { return (double)bn[0][c] / std::sqrt((double)bn[3][c] + eps); }
+
+}  // namespace
+
+extern "C" size_t og_superpoint_packed_bytes(int32_t descriptor_dim) {
+    if (descriptor_dim != SP_D) return 0;
+    return (size_t)sp_layout().total * 4;
+}
+
+// params: 24 host pointers, the weight and bias of conv1a, conv1b, ..., conv4b, convPa, convPb, convDa, convDb; with batch_norm
+// 48 more, weight / bias / running_mean / running_var of bn1a, ..., bn4b, bnPa, bnPb, bnDa, bnDb.
+extern "C" int og_superpoint_pack(int32_t descriptor_dim, int32_t batch_norm, float bn_eps, const float* const* params, void* packed_host) {
+    if (descriptor_dim != SP_D) return OG_E_SHAPE;
+    if (!params || !packed_host) return OG_E_INVALID;
+    const int nconv = 12;
+    for (int i = 0; i < nconv * 2 + (batch_norm ? nconv * 4 : 0); ++i)
+        if (!params[i]) return OG_E_INVALID;
+    const SpLayout L = sp_layout();
+    float* P = (float*)packed_host;
+    bool finite = true;
+    // folded weight / bias of conv i, output channel co: W * s, (b - mean) * s + beta
+    auto scale = [&](int i, int co) -> double { return batch_norm ? fold_scale(params + nconv * 2 + i * 4, co, bn_eps) : 1.0; };
+    auto shift = [&](int i, int co) -> double {
+        const double b = params[2 * i + 1][co];
+        if (!batch_norm) return b;
+        const float* const* bn = params + nconv * 2 + i * 4;
+        return (b - bn[2][co]) * scale(i, co) + bn[1][co];
+    };
+    auto put = [&](int64_t o, double v) {
+        const float f = (float)v;
+        finite = finite && std::isfinite(f);
+        P[o] = f;
+    };
+    // conv1a: [tap][64]
+    for (int co = 0; co < 64; ++co) {
+        for (int t = 0; t < 9; ++t) put(L.w1a + t * 64 + co, (double)params[0][co * 9 + t] * scale(0, co));
+        put(L.b1a + co, shift(0, co));
+    }
+    // 3x3 convs, fragment-major; heads: convPa (conv 8) rows 0..255, convDa (conv 10) rows 256..511
+    for (int l = 0; l < 8; ++l) {
+        const int Cin = kCin[l], Cout = kCout[l], nsteps = 9 * Cin / 8;
+        for (int co = 0; co < Cout; ++co) {
+            const int ci_conv = l < 7 ? l + 1 : (co < 256 ? 8 : 10);
+            const int row = l < 7 ? co : co % 256;
+            const float* w = params[2 * ci_conv];
+            const double sc = scale(ci_conv, row);
+            put(L.b[l] + co, shift(ci_conv, row));
+            for (int s = 0; s < nsteps; ++s) {
+                const int chunk = s / 36, tap = (s / 4) % 9, kk = s % 4;
+                for (int h = 0; h < 2; ++h)
+                    for (int e = 0; e < 4; ++e) {
+                        const int ci = chunk * 32 + kk * 8 + 4 * h + e;
+                        const int lanei = (co & 31) + 32 * h;
+                        put(L.w[l] + (((int64_t)(co / 32) * nsteps + s) * 64 + lanei) * 4 + e, (double)w[((int64_t)row * Cin + ci) * 9 + tap] * sc);
+                    }
+            }
+        }
+    }
+    // cell: tiles 0..2 convPb (conv 9, 65 rows, zero-padded to 96), tiles 3..10 convDb (conv 11)
+    for (int t = 0; t < SP_P_TILES + SP_D_TILES; ++t)
+        for (int j = 0; j < 32; ++j) {
+            const bool isP = t < SP_P_TILES;
+            const int row = (isP ? t : t - SP_P_TILES) * 32 + j;
+            const bool live = !isP || row < 65;
+            const int ic = isP ? 9 : 11;
+            const double sc = live ? scale(ic, row) : 0.0;
+            put(L.bc + (isP ? 0 : 32 * SP_P_TILES) + row, live ? shift(ic, row) : 0.0);
+            for (int s = 0; s < 32; ++s)
+                for (int h = 0; h < 2; ++h)
+                    for (int e = 0; e < 4; ++e) {
+                        const int ci = s * 8 + 4 * h + e;
+                        put(L.wc + (((int64_t)t * 32 + s) * 64 + j + 32 * h) * 4 + e, live ? (double)params[2 * ic][row * 256 + ci] * sc : 0.0);
+                    }
+        }
+    return finite ? 0 : OG_E_RANGE;
+}
+
+extern "C" int og_superpoint_capacity(int32_t H, int32_t W, int32_t max_kpts) {
+    if (H < 8 || W < 8) return 0;
+    return (int)sp_capacity(H / 8 * 8, W / 8 * 8, max_kpts);
+}
+
+extern "C" size_t og_superpoint_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t nms_kernel, int32_t max_kpts) {
+    (void)nms_kernel;
+    (void)max_kpts;
+    if (!dense_shape_ok(batch, H, W)) return 0;
+    const size_t det = detect_layout(nullptr, batch, H / 8 * 8, W / 8 * 8).bytes;
+    const size_t den = dense_bytes(batch, H, W);
+    return det > den ? det : den;
+}
+
+extern "C" int og_superpoint_dense(int32_t batch, int32_t H, int32_t W, const float* image, const void* packed_dev, float* heatmap,
+                                   float* coarse_desc, void* workspace_dev, void* stream) {
+    og_clear_status();
+    if (!image || !packed_dev || !heatmap || !coarse_desc || !workspace_dev) return OG_E_INVALID;
+    if (!dense_shape_ok(batch, H, W)) return OG_E_SHAPE;
+    if ((uintptr_t)packed_dev % 16 || (uintptr_t)coarse_desc % 16 || (uintptr_t)workspace_dev % 16) return OG_E_ALIGN;
+    const SpLayout L = sp_layout();
+    const float* P = (const float*)packed_dev;
+    const Dims d = dims(H, W);
+    hipStream_t st = (hipStream_t)stream;
+    float* X = (float*)workspace_dev;
+    float* Y = (float*)((char*)workspace_dev + og_round_up((int64_t)batch * H * W * 64 * 4, 256));
+    const int64_t n1a = (int64_t)batch * H * W * 16;
+    hipLaunchKernelGGL(sp_conv1a_kernel, dim3((unsigned)((n1a + 255) / 256)), dim3(256), 0, st, image, P + L.w1a, P + L.b1a, batch, H, W, X);
+    conv<64, true>(X, P + L.w[0], P + L.b[0], batch, H, W, 64, 64, Y, st);             // conv1b + pool
+    conv<64, false>(Y, P + L.w[1], P + L.b[1], batch, d.H2, d.W2, 64, 64, X, st);      // conv2a
+    conv<64, true>(X, P + L.w[2], P + L.b[2], batch, d.H2, d.W2, 64, 64, Y, st);       // conv2b + pool
+    conv<128, false>(Y, P + L.w[3], P + L.b[3], batch, d.H4, d.W4, 64, 128, X, st);    // conv3a
+    conv<128, true>(X, P + L.w[4], P + L.b[4], batch, d.H4, d.W4, 128, 128, Y, st);    // conv3b + pool
+    conv<128, false>(Y, P + L.w[5], P + L.b[5], batch, d.Hc, d.Wc, 128, 128, X, st);   // conv4a
+    conv<128, false>(X, P + L.w[6], P + L.b[6], batch, d.Hc, d.Wc, 128, 128, Y, st);   // conv4b
+    conv<128, false>(Y, P + L.w[7], P + L.b[7], batch, d.Hc, d.Wc, 128, 512, X, st);   // convPa | convDa
+    const int npix = batch * d.Hc * d.Wc;
+    hipLaunchKernelGGL(sp_cell_kernel, dim3((npix + SP_CELL_PIX - 1) / SP_CELL_PIX), dim3(256), 0, st, X, P + L.wc, P + L.bc, npix, d.Hc, d.Wc,
+                       heatmap, coarse_desc);
+    return og_launch_status();
+}
+
+extern "C" int og_superpoint_detect(int32_t batch, int32_t Hh, int32_t Wh, int32_t nms_kernel, int32_t border, float threshold,
+                                    int32_t max_kpts, const float* heatmap, int32_t* counts, int32_t* sel_idx, float* sel_score,
+                                    int64_t sel_ld, void* workspace_dev, void* stream) {
+    og_clear_status();
+    if (!heatmap || !counts || !sel_idx || !sel_score || !workspace_dev) return OG_E_INVALID;
+    if (batch <= 0 || Hh < 8 || Wh < 8 || Hh % 8 || Wh % 8 || (int64_t)batch * Hh * Wh > (1ll << 26)) return OG_E_SHAPE;
+    if (nms_kernel < 3 || nms_kernel % 2 == 0 || (nms_kernel - 1) / 2 > SP_NMS_RMAX || border < 0 || max_kpts < -1) return OG_E_SHAPE;
+    if (sel_ld < sp_capacity(Hh, Wh, max_kpts)) return OG_E_INVALID;
+    if ((uintptr_t)workspace_dev % 16) return OG_E_ALIGN;
+    hipStream_t st = (hipStream_t)stream;
+    const DetectWs w = detect_layout(workspace_dev, batch, Hh, Wh);
+    const int64_t cap = sp_capacity(Hh, Wh, -1);
+    const int nseg = (Wh + SP_NMS_SEG - 1) / SP_NMS_SEG;
+    const dim3 grid(nseg, Hh, batch);
+    hipLaunchKernelGGL(sp_nms_kernel, grid, dim3(256), 0, st, heatmap, Hh, Wh, (nms_kernel - 1) / 2, border, threshold, w.mask, w.seg);
+    hipLaunchKernelGGL(sp_scan_kernel, dim3(batch), dim3(256), 0, st, w.seg, Hh * nseg, w.counts);
+    hipLaunchKernelGGL(sp_compact_kernel, grid, dim3(256), 0, st, heatmap, w.mask, Hh, Wh, w.seg, cap, w.cand_idx, w.cand_score);
+    hipLaunchKernelGGL(sp_select_kernel, dim3((unsigned)((cap + 255) / 256), batch), dim3(256), 0, st, w.counts, batch, max_kpts, cap,
+                       w.cand_idx, w.cand_score, sel_ld, counts, sel_idx, sel_score);
+    return og_launch_status();
+}
+
+extern "C" int og_superpoint_describe(int32_t batch, int32_t Hc, int32_t Wc, int32_t n, const int32_t* sel_idx, const float* sel_score,
+                                      int64_t sel_ld, const float* coarse_desc, float* lafs, float* scores, float* descriptors, void* stream) {
+    og_clear_status();
+    if (batch <= 0 || Hc <= 0 || Wc <= 0 || n < 0 || sel_ld < n) return OG_E_SHAPE;
+    if (n == 0) return 0;
+    if (!sel_idx || !sel_score || !coarse_desc || !lafs || !scores || !descriptors) return OG_E_INVALID;
+    if ((uintptr_t)coarse_desc % 16 || (uintptr_t)descriptors % 16) return OG_E_ALIGN;
+    hipLaunchKernelGGL(sp_describe_kernel, dim3((n + 3) / 4, batch), dim3(256), 0, (hipStream_t)stream, batch, Hc, Wc, n, sel_idx, sel_score,
+                       sel_ld, coarse_desc, lafs, scores, descriptors);
+    return og_launch_status();
+}

@@ -240,3 +240,94 @@ def ragged_lengths(batch: int, lo: int, hi: int, seed: int = 0) -> List[tuple]:
     g = torch.Generator().manual_seed(77_777 + seed)
     t = torch.randint(lo, hi + 1, (batch, 2), generator=g)
     return [(int(a), int(b)) for a, b in t.tolist()]
+
+
+# ---------------------------------------------------------------- SuperPoint inputs (openglue_amd/superpoint.py)
+def make_image(H: int, W: int, seed: int, shapes: int = 24, flat: bool = False) -> torch.Tensor:
+    """[1, 1, H, W] in [0, 1]: filled convex polygons and ellipses of random grey levels over a grey background, blurred
+    (Gaussian, sigma 1 px), with mild noise (sigma 0.01).  flat=True draws a few faint, large shapes and no noise: a sparse image."""
+    g = torch.Generator().manual_seed(seed)
+    U = lambda *s: torch.rand(*s, generator=g)
+    yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    img = torch.full((H, W), 0.5 if flat else float(U(1)) * 0.6 + 0.2, dtype=torch.float64)
+    n = 3 if flat else shapes
+    for _ in range(n):
+        cx, cy = float(U(1)) * W, float(U(1)) * H
+        r = (0.25 + 0.35 * float(U(1))) * min(H, W) if flat else (0.04 + 0.16 * float(U(1))) * min(H, W)
+        level = 0.5 + (float(U(1)) - 0.5) * 0.08 if flat else float(U(1))
+        if float(U(1)) < 0.5:       # ellipse
+            a, b, th = r, r * (0.3 + 0.7 * float(U(1))), float(U(1)) * math.pi
+            u = (xx - cx) * math.cos(th) + (yy - cy) * math.sin(th)
+            v = -(xx - cx) * math.sin(th) + (yy - cy) * math.cos(th)
+            inside = (u / a) ** 2 + (v / b) ** 2 <= 1.0
+        else:                       # convex polygon: 3..7 vertices on a circle
+            k = 3 + int(U(1) * 5)
+            ang = torch.sort(U(k) * 2 * math.pi).values
+            px, py = cx + r * torch.cos(ang), cy + r * torch.sin(ang)
+            inside = torch.ones(H, W, dtype=torch.bool)
+            for i in range(k):
+                x0, y0, x1, y1 = float(px[i]), float(py[i]), float(px[(i + 1) % k]), float(py[(i + 1) % k])
+                inside &= (x1 - x0) * (yy - y0) - (y1 - y0) * (xx - x0) >= 0
+        img = torch.where(inside, torch.tensor(level, dtype=torch.float64), img)
+    t = torch.arange(-3, 4, dtype=torch.float64)
+    k1 = torch.exp(-t * t / 2.0)
+    k1 = k1 / k1.sum()
+    x = torch.nn.functional.pad(img[None, None], (3, 3, 3, 3), mode="replicate")
+    x = torch.nn.functional.conv2d(x, k1.view(1, 1, 1, 7))
+    x = torch.nn.functional.conv2d(x, k1.view(1, 1, 7, 1))
+    x = x + (0.0 if flat else 0.01) * torch.randn(x.shape, generator=g, dtype=torch.float64)
+    return x.clamp(0.0, 1.0).to(torch.float32)
+
+
+def random_homography(H: int, W: int, seed: int, strength: float = 0.12) -> torch.Tensor:
+    """[3, 3] float64 mapping pixel (x, y, 1) of image 0 to image 1: the image corners moved by up to strength * size."""
+    g = torch.Generator().manual_seed(seed)
+    src = torch.tensor([[0.0, 0.0], [W - 1.0, 0.0], [W - 1.0, H - 1.0], [0.0, H - 1.0]], dtype=torch.float64)
+    dst = src + (torch.rand(4, 2, generator=g, dtype=torch.float64) - 0.5) * 2 * strength * torch.tensor([W, H], dtype=torch.float64)
+    A = []
+    for (x, y), (u, v) in zip(src.tolist(), dst.tolist()):
+        A.append([x, y, 1, 0, 0, 0, -u * x, -u * y, -u])
+        A.append([0, 0, 0, x, y, 1, -v * x, -v * y, -v])
+    _, _, vh = torch.linalg.svd(torch.tensor(A, dtype=torch.float64))
+    Hm = vh[-1].view(3, 3)
+    return Hm / Hm[2, 2]
+
+
+def warp_image(image: torch.Tensor, Hm: torch.Tensor) -> torch.Tensor:
+    """Second view of a pair: out(p) = image(Hm^-1 p), bilinear, border pixels replicated.  image [1, 1, H, W]."""
+    _, _, H, W = image.shape
+    yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float64), torch.arange(W, dtype=torch.float64), indexing="ij")
+    p = torch.stack([xx, yy, torch.ones_like(xx)], -1) @ torch.linalg.inv(Hm).T
+    sx, sy = p[..., 0] / p[..., 2], p[..., 1] / p[..., 2]
+    grid = torch.stack([sx / (W - 1) * 2 - 1, sy / (H - 1) * 2 - 1], -1)[None]
+    out = torch.nn.functional.grid_sample(image.to(torch.float64), grid, mode="bilinear", padding_mode="border", align_corners=True)
+    return out.to(torch.float32)
+
+
+def make_superpoint_state_dict(batch_norm: bool = False, seed: int = 0, descriptor_dim: int = 256) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded SuperPoint weights with a realistic heatmap.  PyTorch's default init collapses the 65-way softmax to ~1/65
+    everywhere (every NMS decision a near-tie); here the trunk is He-normal and convPb is scaled up so that the detector's
+    logits spread over several units.  With batch_norm the BatchNorm affine parameters and running statistics are randomised
+    around the identity."""
+    g = torch.Generator().manual_seed(seed)
+    chans = [(1, 64), (64, 64), (64, 64), (64, 64), (64, 128), (128, 128), (128, 128), (128, 128)]
+    names = [f"conv{i}{s}" for i in range(1, 5) for s in "ab"]
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+    convs = list(zip(names, chans, [3] * 8)) + [("convPa", (128, 256), 3), ("convPb", (256, 65), 1),
+                                                ("convDa", (128, 256), 3), ("convDb", (256, descriptor_dim), 1)]
+    for name, (cin, cout), k in convs:
+        std = math.sqrt(2.0 / (cin * k * k))
+        if name == "convPb":
+            std *= 6.0
+        sd[f"{name}.weight"] = torch.randn(cout, cin, k, k, generator=g) * std
+        sd[f"{name}.bias"] = torch.randn(cout, generator=g) * 0.01
+    if batch_norm:
+        bns = [(f"bn{i}{s}", c) for i, (s, c) in zip([1, 1, 2, 2, 3, 3, 4, 4], [("a", 64), ("b", 64)] * 2 + [("a", 128), ("b", 128)] * 2)]
+        bns += [("bnPa", 256), ("bnPb", 65), ("bnDa", 256), ("bnDb", descriptor_dim)]
+        for name, c in bns:
+            sd[f"{name}.weight"] = 0.8 + 0.4 * torch.rand(c, generator=g)
+            sd[f"{name}.bias"] = torch.randn(c, generator=g) * 0.05
+            sd[f"{name}.running_mean"] = torch.randn(c, generator=g) * 0.05
+            sd[f"{name}.running_var"] = 0.8 + 0.4 * torch.rand(c, generator=g)
+            sd[f"{name}.num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+    return sd
