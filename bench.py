@@ -2,7 +2,7 @@
 """Benchmark of the SuperGlue hot path on MI355X: matched image-pairs / second.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C1|C3|C4|C5] [--batch PAIRS_PER_GPU | --global-batch PAIRS]
-                    [--no-cpu-baseline] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-training-step]] [--dump-outputs DIR]
 
 With --gpus N > 1 and no torch.distributed environment the script re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one process per GPU,
@@ -13,6 +13,11 @@ A step = one pass of the whole hot path (keypoint encoder -> 9x(self, cross) att
 100 Sinkhorn iterations -> mutual-NN matches) over one batch of synthetic pairs already resident in
 HBM, plus (N > 1) the single RCCL gather of the match lists on rank 0.  Weak scaling: every rank
 processes its own batch of the configured size.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, --dump-outputs, the line.
+--full also measures, after the timed steps and in runs of their own: the per-step spread, per-kernel-class times and the
+roofline, the step fed from host buffers, the training steps (C2 at its default batch, one GPU), the CPU baseline (one GPU)
+and, with N > 1, every rank's step time with and without the collective.
 """
 import argparse
 import ctypes as C
@@ -525,11 +530,13 @@ def dump_outputs(out, dirname):
 
 
 def _measure(step, step_compute, args, dist_on, dev):
-    """The part of a bench run EVERY rank executes, in this order: the timed region, the per-step spread, the per-rank times of the rccl block.
-    `step` holds the collective when N > 1, so nothing here may run on rank 0 alone (round 4 computed the spread inside `if rank == 0`: with more
-    than one rank it would have waited in the gather for ever).  The gloo dry run (tests/test_sharding_cpu.py, 2 and 8 ranks) drives this very
-    function with a stub matcher."""
+    """The part of a bench run EVERY rank executes, in this order: the timed region and, with --full, the per-step spread and the per-rank times
+    of the rccl block (a plain run returns no spread and the rccl block without times).  `step` holds the collective when N > 1, so nothing here
+    may run on rank 0 alone (round 4 computed the spread inside `if rank == 0`: with more than one rank it would have waited in the gather for
+    ever).  The gloo dry run (tests/test_sharding_cpu.py, 2 and 8 ranks) drives this very function with a stub matcher."""
     dt, out = _timed_steps(step, args, dist_on, dev)
+    if not args.full:
+        return dt, out, None, _rccl_block(dist_on)
     spread = _step_spread(step, args.steps, dev)
     rccl = _rccl_block(dist_on, step_compute, step, dev)
     return dt, out, spread, rccl
@@ -566,37 +573,37 @@ def bench_ragged(args, world, rank, dev, dist_on=False):
 
     dt, out, spread, rccl = _measure(step, lambda: match_mine(mine), args, dist_on, dev)
     if rank == 0:
-        res = match_mine(mine)
+        res = match_mine(mine) if dist_on else out          # this rank's per-pair results (the step returns them itself without the gather)
         my_lens = [lens[i] for i in mine]
         counts = _sum_counts(kw, my_lens)
-
-        def run_profiled():
-            ms = (C.c_float * len(_lib.OG_STAGES))(); cnt = (C.c_int32 * len(_lib.OG_STAGES))()
-            model.match_ragged_packed(packed, MATCH_THRESHOLD, both_sides=False, _profile=(ms, cnt))
-            return _stage_dict(ms, cnt)
-        stages, launches = _median_stages(run_profiled)
-        a0 = (C.c_int32 * len(my_lens))(*[a for a, _ in my_lens]); a1 = (C.c_int32 * len(my_lens))(*[b for _, b in my_lens])
-        sk_launches = int(_lib.load().og_sinkhorn_schedule_ragged(len(my_lens), a0, a1, kw["num_iters"])) if len(my_lens) <= 64 else 0
-        roof, roof2 = roofline_block(counts, stages, launches, kw["num_iters"], False, sk_launches)
         line = {"metric": "image-pairs/sec (C5 ragged 512-2048 kpts)", "value": round(total * args.steps / dt, 2), "unit": "image-pairs/s",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-                "step_ms_spread": spread,
                 "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+                "full": args.full,
                 "config": {"workload": f"BASELINE configs[4]: {total} ragged pairs ({per_gpu}/GPU), 512-2048 kpts/image, 256-dim, 9 stages, "
                                        "100 Sinkhorn iters, token-packed ragged kernels (og_forward_ragged), LPT cost-balanced over ranks",
                            "arithmetic": ARITHMETIC, "global_batch": total,
                            "mean_kpts": round(sum(a + b for a, b in lens) / (2 * total), 1), "pairs_per_gpu": per_gpu},
                 "rccl": rccl,
-                "roofline": roof, "roofline_other": roof2, "stages_ms": {k: round(v, 3) for k, v in stages.items()},
                 "algorithmic": {"gflop_per_step_rank0": round(counts["total_flops"] / 1e9, 2),
                                 "sinkhorn_gb_per_step_rank0": round(counts["sinkhorn_bytes"] / 1e9, 3)},
                 "valid_matches_per_pair": round(sum(int((r["matches0"] >= 0).sum()) for r in res) / max(1, len(res)), 1)}
-        if world == 1 and not args.no_cpu_baseline:   # the mean-size pair of the job as the CPU sample
-            mm = int(round(sum(a for a, _ in lens) / total)); nn_ = int(round(sum(b for _, b in lens) / total))
-            line["cpu_baseline"] = cpu_baseline(cfg, sd, kw, mm, nn_)
-            line["cpu_baseline"]["sample"] += f" [one {mm}x{nn_}-keypoint pair = the mean size of the ragged job]"
-        else:
-            line["cpu_baseline"] = None
+        if args.full:
+            def run_profiled():
+                ms = (C.c_float * len(_lib.OG_STAGES))(); cnt = (C.c_int32 * len(_lib.OG_STAGES))()
+                model.match_ragged_packed(packed, MATCH_THRESHOLD, both_sides=False, _profile=(ms, cnt))
+                return _stage_dict(ms, cnt)
+            stages, launches = _median_stages(run_profiled)
+            a0 = (C.c_int32 * len(my_lens))(*[a for a, _ in my_lens]); a1 = (C.c_int32 * len(my_lens))(*[b for _, b in my_lens])
+            sk_launches = int(_lib.load().og_sinkhorn_schedule_ragged(len(my_lens), a0, a1, kw["num_iters"])) if len(my_lens) <= 64 else 0
+            roof, roof2 = roofline_block(counts, stages, launches, kw["num_iters"], False, sk_launches)
+            line.update(step_ms_spread=spread, roofline=roof, roofline_other=roof2, stages_ms={k: round(v, 3) for k, v in stages.items()})
+            if world == 1 and not args.no_cpu_baseline:   # the mean-size pair of the job as the CPU sample
+                mm = int(round(sum(a for a, _ in lens) / total)); nn_ = int(round(sum(b for _, b in lens) / total))
+                line["cpu_baseline"] = cpu_baseline(cfg, sd, kw, mm, nn_)
+                line["cpu_baseline"]["sample"] += f" [one {mm}x{nn_}-keypoint pair = the mean size of the ragged job]"
+            else:
+                line["cpu_baseline"] = None
         if args.dump_outputs:
             dump_outputs(out, args.dump_outputs)
         _flush_c_stdio()              # RCCL's version banner sits in the C library's stdout buffer: get it out BEFORE the line, which stays the last one
@@ -664,8 +671,10 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="pairs per GPU (default: the config's)")
     ap.add_argument("--global-batch", type=int, default=None,
                     help="pairs of the whole job, split evenly over the ranks (BASELINE: C3 256, C4 64, C5 128 over 8 GPUs) -- strong scaling")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-training-step", action="store_true", help="skip the informational training-step leg (C2, N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline figure does not need (spread, roofline, training steps, CPU baseline, ...)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-training-step", action="store_true", help="--full without the informational training-step leg (C2, N = 1 only)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the run, write what the last timed step returned (rank 0) as DIR/<name>.npy, at most 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
@@ -721,25 +730,14 @@ def main():
 
     if rank == 0:
         c1 = algorithmic_counts(kw, m, n)
-        counts = {k: v * B for k, v in c1.items()}
         ms_per_step = dt / args.steps * 1e3
         value = world * B * args.steps / dt
-
-        def run_profiled():     # per-kernel-class time of one step, HIP events on the launch stream
-            ms = (C.c_float * len(_lib.OG_STAGES))(); cnt = (C.c_int32 * len(_lib.OG_STAGES))()
-            model.match(data, MATCH_THRESHOLD, both_sides=True, _profile=(ms, cnt))
-            return _stage_dict(ms, cnt)
-        stages, launches = _median_stages(run_profiled)
-        sk_launches = int(_lib.load().og_sinkhorn_schedule(B, m, n, kw["num_iters"]))
-        std_batch = B == syn.CONFIGS[args.config]["batch"]
-        roof, roof2 = roofline_block(counts, stages, launches, kw["num_iters"], args.config == "C2" and std_batch, sk_launches,
-                                     TRAFFIC_BY_CONFIG.get(args.config) if std_batch else None)
         line = {
             "metric": "image-pairs/sec (1024 kpts, 256-dim, 9 GNN layers)" if args.config == "C2" else f"image-pairs/sec ({args.config})",
             "value": round(value, 2), "unit": "image-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 3), "step_ms_spread": spread,
+            "ms_per_step": round(ms_per_step, 3),
             "higher_is_better": True, "scaling": "strong" if args.global_batch else "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
+            "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": ({"S128": "the reference's shipped 128-d operating point (config/features/sift_opencv.yaml:2-4, config/config.yaml:53), not a BASELINE config: ",
                                      "S256": "the reference's shipped 256-d operating point (config/features/superpoint_magicleap.yaml:2-4, config/config.yaml:53), not a BASELINE config: ",
                                      "C4i20": "BASELINE configs[3] at the reference's default 20 Sinkhorn iterations (config/config.yaml:53; C4 runs 100): "}.get(
@@ -749,51 +747,62 @@ def main():
                        "arithmetic": ARITHMETIC, "global_batch": world * B,
                        "pairs_per_gpu": B, "kpts": [m, n], "parallelism": f"pairs sharded over {world} GPU(s), 1 RCCL gather"},
             "rccl": rccl,
-            "roofline": roof, "roofline_other": roof2,
-            "stages_ms": {k: round(v, 3) for k, v in stages.items()},
             "algorithmic": {"gflop_per_pair": round(c1["total_flops"] / 1e9, 2), "sinkhorn_gb_per_pair": round(c1["sinkhorn_bytes"] / 1e9, 3),
                             "sinkhorn_gb_per_pair_survey_two_sweeps": round(c1["sinkhorn_bytes_survey"] / 1e9, 3)},
             "valid_matches_per_pair": round(float((out["matches0"] >= 0).sum().item()) / B, 1),
         }
-        # The same step fed from pinned HOST buffers, H2D of keypoints/descriptors/side-info included and double-buffered
-        # on a copy stream (batch k+1 uploads while batch k computes).  The boundary hands over device tensors, so this is
-        # informational and never `value`.
-        host = {k: v.cpu().pin_memory() for k, v in data.items() if torch.is_tensor(v)}
-        copy_stream = torch.cuda.Stream(device=dev)
-        bufs = [{k: torch.empty_like(v, device=dev) for k, v in host.items()} for _ in range(2)]
-        ready = [torch.cuda.Event() for _ in range(2)]
-        freed = [torch.cuda.Event() for _ in range(2)]
+        if args.full:
+            counts = {k: v * B for k, v in c1.items()}
 
-        def upload(i):
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(freed[i])            # the step that read this buffer has finished
-                for k, v in host.items():
-                    bufs[i][k].copy_(v, non_blocking=True)
-                ready[i].record(copy_stream)
-        for i in range(2):
-            freed[i].record(torch.cuda.current_stream(dev))
-        upload(0)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for s_ in range(args.steps):
-            i = s_ & 1
-            if s_ + 1 < args.steps:
-                upload(i ^ 1)
-            torch.cuda.current_stream(dev).wait_event(ready[i])
-            d = dict(bufs[i]); d["image0_size"], d["image1_size"] = data["image0_size"], data["image1_size"]
-            model.match(d, MATCH_THRESHOLD, both_sides=True)
-            freed[i].record(torch.cuda.current_stream(dev))
-        torch.cuda.synchronize()
-        line["value_incl_h2d"] = round(B * args.steps / (time.perf_counter() - t0), 2)
-        # only in the driver's own invocation (C2 at its default batch, one GPU): sweeps over --batch / --config and profiler runs stay what they name
-        want_train = world == 1 and args.config == "C2" and args.batch is None and args.global_batch is None and not args.no_training_step
-        line["training_step"] = _training_step(dev) if want_train else None
-        # ... and at the reference's OWN training shape: batch_size_per_gpu 2 (config/config.yaml:12) x up to 2048 keypoints, 20 iterations
-        line["training_step_reference_shape"] = _training_step(dev, B=2, N=2048, iters=20, steps=5) if want_train else None
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(cfg, sd, kw, m, n)
-        else:
-            line["cpu_baseline"] = None
+            def run_profiled():     # per-kernel-class time of one step, HIP events on the launch stream
+                ms = (C.c_float * len(_lib.OG_STAGES))(); cnt = (C.c_int32 * len(_lib.OG_STAGES))()
+                model.match(data, MATCH_THRESHOLD, both_sides=True, _profile=(ms, cnt))
+                return _stage_dict(ms, cnt)
+            stages, launches = _median_stages(run_profiled)
+            sk_launches = int(_lib.load().og_sinkhorn_schedule(B, m, n, kw["num_iters"]))
+            std_batch = B == syn.CONFIGS[args.config]["batch"]
+            roof, roof2 = roofline_block(counts, stages, launches, kw["num_iters"], args.config == "C2" and std_batch, sk_launches,
+                                         TRAFFIC_BY_CONFIG.get(args.config) if std_batch else None)
+            line.update(step_ms_spread=spread, roofline=roof, roofline_other=roof2, stages_ms={k: round(v, 3) for k, v in stages.items()})
+            # The same step fed from pinned HOST buffers, H2D of keypoints/descriptors/side-info included and double-buffered
+            # on a copy stream (batch k+1 uploads while batch k computes).  The boundary hands over device tensors, so this is
+            # informational and never `value`.
+            host = {k: v.cpu().pin_memory() for k, v in data.items() if torch.is_tensor(v)}
+            copy_stream = torch.cuda.Stream(device=dev)
+            bufs = [{k: torch.empty_like(v, device=dev) for k, v in host.items()} for _ in range(2)]
+            ready = [torch.cuda.Event() for _ in range(2)]
+            freed = [torch.cuda.Event() for _ in range(2)]
+
+            def upload(i):
+                with torch.cuda.stream(copy_stream):
+                    copy_stream.wait_event(freed[i])            # the step that read this buffer has finished
+                    for k, v in host.items():
+                        bufs[i][k].copy_(v, non_blocking=True)
+                    ready[i].record(copy_stream)
+            for i in range(2):
+                freed[i].record(torch.cuda.current_stream(dev))
+            upload(0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for s_ in range(args.steps):
+                i = s_ & 1
+                if s_ + 1 < args.steps:
+                    upload(i ^ 1)
+                torch.cuda.current_stream(dev).wait_event(ready[i])
+                d = dict(bufs[i]); d["image0_size"], d["image1_size"] = data["image0_size"], data["image1_size"]
+                model.match(d, MATCH_THRESHOLD, both_sides=True)
+                freed[i].record(torch.cuda.current_stream(dev))
+            torch.cuda.synchronize()
+            line["value_incl_h2d"] = round(B * args.steps / (time.perf_counter() - t0), 2)
+            # only in the driver's own invocation (C2 at its default batch, one GPU): sweeps over --batch / --config and profiler runs stay what they name
+            want_train = world == 1 and args.config == "C2" and args.batch is None and args.global_batch is None and not args.no_training_step
+            line["training_step"] = _training_step(dev) if want_train else None
+            # ... and at the reference's OWN training shape: batch_size_per_gpu 2 (config/config.yaml:12) x up to 2048 keypoints, 20 iterations
+            line["training_step_reference_shape"] = _training_step(dev, B=2, N=2048, iters=20, steps=5) if want_train else None
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(cfg, sd, kw, m, n)
+            else:
+                line["cpu_baseline"] = None
         if args.dump_outputs:
             dump_outputs(out, args.dump_outputs)
         _flush_c_stdio()              # RCCL's version banner sits in the C library's stdout buffer: get it out BEFORE the line, which stays the last one

@@ -10,7 +10,7 @@ REPS=${REPS:-2}
 rm -f $OUT/ab.jsonl
 for r in $(seq 1 $REPS); do
   for v in "$@"; do
-    env $VAR=$v timeout 600 python bench.py --steps 30 --warmup 5 --no-cpu-baseline ${CFG:-} 2>/dev/null | tail -1 | python -c "
+    env $VAR=$v timeout 600 python bench.py --full --steps 30 --warmup 5 --no-cpu-baseline ${CFG:-} 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); print(json.dumps({'var': '$VAR', 'val': '$v', 'value': d['value'], 'ms': d['ms_per_step'], 'stages': d['stages_ms']}))" | tee -a $OUT/ab.jsonl
   done

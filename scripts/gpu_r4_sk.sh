@@ -12,7 +12,7 @@ for shape in 32,1024,1024,100 8,2048,2048,100 2,4096,4096,100; do
   echo "== trace $shape"; OG_SK_SHAPE=$shape OPENGLUE_AMD_LIB=openglue_amd/lib/libog_sk_trace.so timeout 300 python scripts/trace_sinkhorn.py 2>&1 | grep -v amdgpu.ids
 done
 if [ "${2:-}" = "full" ]; then
-  for c in C2 C3 C4 C5; do echo "== bench $c"; timeout 600 python bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stages_ms'])"; done
+  for c in C2 C3 C4 C5; do echo "== bench $c"; timeout 600 python bench.py --full --config $c --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['stages_ms'])"; done
 fi
 } > $OUT 2>&1
 tail -150 $OUT

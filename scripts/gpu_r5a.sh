@@ -14,10 +14,10 @@ tail -30 $OUT/${TAG}_pytest_gpu.log
 for env in "" "OG_MLP_FUSED=0" ; do
   for cfg in "C4" "S128" "S128 --batch 1" "S128 --batch 4"; do
     echo "== $env $cfg" | tee -a $OUT/${TAG}_bench_ab.jsonl
-    env $env timeout 600 python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
+    env $env timeout 600 python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
   done
 done
-env OG_PROJ_SMALL=0 OG_MLP_SMALL=0 timeout 600 python bench.py --config S128 --batch 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
+env OG_PROJ_SMALL=0 OG_MLP_SMALL=0 timeout 600 python bench.py --full --config S128 --batch 1 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
 python - <<PY
 import json
 for l in open("gpurun_out/${TAG}_bench_ab.jsonl"):
@@ -26,7 +26,7 @@ for l in open("gpurun_out/${TAG}_bench_ab.jsonl"):
     except Exception: print("bad line", l[:200]); continue
     print(d["metric"], d["config"].get("pairs_per_gpu"), d["value"], d["ms_per_step"], d["stages_ms"], "| roofline", d["roofline"]["kernel"], d["roofline"]["frac"])
 PY
-timeout 900 python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
+timeout 900 python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
 python - <<PY
 import json
 d = json.loads(open("gpurun_out/${TAG}_bench.json").read()); print("BENCH", d["value"], d["ms_per_step"], d["step_ms_spread"], d["stages_ms"], "roofline", d["roofline"]["kernel"], d["roofline"]["frac"], "cpu", d["cpu_baseline"]["value"], d["cpu_baseline"].get("multi_process"))

@@ -13,7 +13,7 @@ tail -25 $OUT/${TAG}_pytest_gpu.log
 for cfg in "C2" "C3" "C4" "S128" "C5"; do
   for env in "OG_PROJ_STREAM=0" "OG_PROJ_STREAM=1" "OG_X=0"; do
     echo "== $env $cfg" >> $OUT/${TAG}_bench_ab.jsonl
-    env $env timeout 600 python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
+    env $env timeout 600 python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
   done
 done
 python - <<PY

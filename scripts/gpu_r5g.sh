@@ -10,7 +10,7 @@ tail -6 $OUT/${TAG}_pytest_sinkhorn.log
 for cfg in "C2 --batch 1" "C2 --batch 2" "C2 --batch 4" "C2 --batch 8" "S128 --batch 1" "C1"; do
   for env in "OG_SINKHORN_FEW=0" "OG_SINKHORN_FEW=1" "OG_X=0"; do
     echo "== $env $cfg" >> $OUT/${TAG}_bench_ab.jsonl
-    env $env timeout 600 python bench.py --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
+    env $env timeout 600 python bench.py --full --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
   done
 done
 python - <<PY

@@ -10,7 +10,7 @@ tail -6 $OUT/${TAG}_pytest_sinkhorn.log
 for cfg in "C2 --batch 12" "C2 --batch 16"; do
   for env in "OG_SINKHORN_FEW=0" "OG_X=0"; do
     echo "== $env $cfg" >> $OUT/${TAG}_bench_ab.jsonl
-    env $env timeout 600 python bench.py --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
+    env $env timeout 600 python bench.py --full --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
   done
 done
 python - <<PY

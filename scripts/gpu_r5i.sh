@@ -15,7 +15,7 @@ grep -E "===|passed|failed|rc=|single-pair" $OUT/${TAG}_pytest.log | head -40
 for cfg in "S128 --batch 1" "S128 --batch 2" "S128 --batch 4" "C4 --batch 1"; do
   for env in "OG_ATTN_GSPLIT=0" "OG_X=0"; do
     echo "== $env $cfg" >> $OUT/${TAG}_bench_ab.jsonl
-    env $env timeout 600 python bench.py --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
+    env $env timeout 600 python bench.py --full --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_ab.jsonl
   done
 done
 python - <<PY

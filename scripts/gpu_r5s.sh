@@ -9,7 +9,7 @@ for rep in 1 2; do
 for cfg in "C2" "C3" "C5"; do
   for env in "OG_X=0" "OG_PROJ_STREAM=2"; do
     echo "== $env $cfg" >> $OUT/r05s_bench_ab.jsonl
-    env $env timeout 600 python bench.py --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 >> $OUT/r05s_bench_ab.jsonl
+    env $env timeout 600 python bench.py --full --config $cfg --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 >> $OUT/r05s_bench_ab.jsonl
   done
 done
 done

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests -m gpu -q --timeout 600 -p no:cacheprovider -
 for rep in 1 2; do
   for env in "OG_RAGGED_PAD=0" "OG_X=0"; do
     echo "== $env C5" >> $OUT/r05t_bench_ab.jsonl
-    env $env timeout 600 python bench.py --config C5 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 >> $OUT/r05t_bench_ab.jsonl
+    env $env timeout 600 python bench.py --full --config C5 --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | tail -1 >> $OUT/r05t_bench_ab.jsonl
   done
 done
 python - <<PY

@@ -16,6 +16,6 @@ done
 cat $OUT/r05v_train_ab.log
 for t in 0 512 100000000; do
   echo "== inference OG_GEMM_F32_NARROW_BELOW=$t"
-  OG_GEMM_F32_NARROW_BELOW=$t timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['stages_ms'])"
-  OG_GEMM_F32_NARROW_BELOW=$t timeout 300 python bench.py --config C2 --batch 1 --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['stages_ms'])"
+  OG_GEMM_F32_NARROW_BELOW=$t timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['stages_ms'])"
+  OG_GEMM_F32_NARROW_BELOW=$t timeout 300 python bench.py --full --config C2 --batch 1 --steps 50 --warmup 10 --no-cpu-baseline 2>/dev/null | grep '^{' | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['stages_ms'])"
 done 2>&1 | tee $OUT/r05v_infer_ab.log

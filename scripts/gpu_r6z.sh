@@ -8,7 +8,7 @@ OUT=gpurun_out; TAG=r06z; mkdir -p $OUT
 timeout 300 python __graft_entry__.py smoke > $OUT/${TAG}_smoke.log 2>&1; tail -1 $OUT/${TAG}_smoke.log
 timeout 2400 python -m pytest tests -m gpu -q --timeout 1200 -p no:cacheprovider > $OUT/${TAG}_pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/${TAG}_pytest_gpu.log
 tail -40 $OUT/${TAG}_pytest_gpu.log > $OUT/${TAG}_pytest_gpu_tail.txt; rm $OUT/${TAG}_pytest_gpu.log; tail -4 $OUT/${TAG}_pytest_gpu_tail.txt
-timeout 900 python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
+timeout 900 python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
 python - <<PY
 import json
 d = json.loads(open("gpurun_out/${TAG}_bench.json").read()); print("BENCH", d["value"], d["ms_per_step"], d["stages_ms"], "roofline", d["roofline"]["kernel"], d["roofline"]["frac"], "cpu", d["cpu_baseline"]["value"])

@@ -14,16 +14,16 @@ if [[ " $* " == *" tests "* ]]; then
   timeout 2400 python -m pytest tests -m gpu -q --timeout 1200 -p no:cacheprovider > $OUT/${TAG}_pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $OUT/${TAG}_pytest_gpu.log
   tail -16 $OUT/${TAG}_pytest_gpu.log
 fi
-timeout 900 python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
+timeout 900 python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
 python - <<PY
 import json
 d = json.loads(open("gpurun_out/${TAG}_bench.json").read()); print("BENCH", d["value"], d["ms_per_step"], d["step_ms_spread"], d["stages_ms"], "roofline", d["roofline"]["kernel"], d["roofline"]["frac"], "cpu", d["cpu_baseline"]["value"])
 PY
 : > $OUT/${TAG}_bench_configs.jsonl
-for c in C1 C3 C4 C5 S128; do timeout 900 python bench.py --config $c --steps 20 --warmup 5 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_configs.jsonl; done
+for c in C1 C3 C4 C5 S128; do timeout 900 python bench.py --full --config $c --steps 20 --warmup 5 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_configs.jsonl; done
 # the reference's own operating point for its 128-d family, ONE pair per call (inference.py:214-235) and four; C2 shape at B = 1 / 2 / 4 / 16 / 64
-for b in 1 4; do timeout 600 python bench.py --config S128 --batch $b --steps 30 --warmup 5 --no-cpu-baseline --no-training-step 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_configs.jsonl; done
-for b in 1 2 4 16 64; do timeout 600 python bench.py --batch $b --steps 30 --warmup 5 --no-cpu-baseline --no-training-step 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_configs.jsonl; done
+for b in 1 4; do timeout 600 python bench.py --full --config S128 --batch $b --steps 30 --warmup 5 --no-cpu-baseline --no-training-step 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_configs.jsonl; done
+for b in 1 2 4 16 64; do timeout 600 python bench.py --full --batch $b --steps 30 --warmup 5 --no-cpu-baseline --no-training-step 2>/dev/null | tail -1 >> $OUT/${TAG}_bench_configs.jsonl; done
 python - <<PY
 import json
 for l in open("gpurun_out/${TAG}_bench_configs.jsonl"):

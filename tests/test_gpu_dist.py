@@ -57,15 +57,18 @@ def test_gather_matches_over_rccl_world1(gpu_device):
 
 
 def test_bench_with_the_collective_forced(gpu_device):
-    """bench.py with the RCCL path forced at world size 1: one JSON line, same metric, the step includes the gather."""
-    env = _env()
-    env.update(OG_BENCH_FORCE_DIST="1", MASTER_PORT="29534")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--batch", "8"],
-                       env=env, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
-    assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
-    line = json.loads(lines[0])
+    """bench.py with the RCCL path forced at world size 1: one JSON line, same metric, the step includes the gather.  --full adds the roofline
+    and the per-rank times; a plain run carries the headline fields and the rccl block without times."""
+    def run(port, *extra):
+        env = _env()
+        env.update(OG_BENCH_FORCE_DIST="1", MASTER_PORT=port)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--batch", "8", *extra],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:] + r.stderr[-2000:]
+        return json.loads(lines[0])
+    line = run("29534", "--full", "--no-cpu-baseline")
     assert line["n_gpus"] == 1 and line["value"] > 0 and "roofline" in line
     # round 5: the rccl block explains a scaling line by itself -- every rank's step time with and without the collective, the gather's own time
     rc = line["rccl"]
@@ -73,6 +76,11 @@ def test_bench_with_the_collective_forced(gpu_device):
     assert len(rc["per_rank_ms_compute_only"]) == 1 and len(rc["per_rank_ms_with_gather"]) == 1 and rc["per_rank_ms_compute_only"][0] > 0
     assert abs(rc["gather_ms_rank0"] - (rc["per_rank_ms_with_gather"][0] - rc["per_rank_ms_compute_only"][0])) < 1e-2
     print("forced-collective bench:", line["value"], line["unit"], line["ms_per_step"], "ms/step")
+    plain = run("29535")
+    assert plain["metric"] == line["metric"] and plain["unit"] == line["unit"] and plain["dtype"] == "f32" and plain["higher_is_better"] is True
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["full"] is False
+    assert plain["rccl"]["backend"] == "nccl" and "per_rank_ms_with_gather" not in plain["rccl"]
+    assert not {"step_ms_spread", "roofline", "stages_ms", "value_incl_h2d", "training_step", "cpu_baseline"} & set(plain)
 
 
 _TWO_RANKS = r'''

@@ -155,7 +155,7 @@ def test_gather_validates_its_arguments():
 
 
 def test_eight_rank_dry_run_of_the_bench_plumbing():
-    """`bench.py --gpus 8` end to end on gloo with the stub matcher (OG_BENCH_DRYRUN=1): self-spawn under torch.distributed.run on
+    """`bench.py --gpus 8 --full` end to end on gloo with the stub matcher (OG_BENCH_DRYRUN=1): self-spawn under torch.distributed.run on
     127.0.0.1, eight ranks, the LPT-balanced ragged shards, ONE gather, ONE JSON line from rank 0 with n_gpus = 8."""
     import json
     import subprocess
@@ -164,7 +164,7 @@ def test_eight_rank_dry_run_of_the_bench_plumbing():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["OG_BENCH_DRYRUN"] = "1"
     env["OMP_NUM_THREADS"] = "1"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "0"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "0", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -181,6 +181,8 @@ def test_eight_rank_dry_run_of_the_bench_plumbing():
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 2 and d["global_batch"] == 10 and d["scaling"] == "strong" and d["gather_ok"] is True
+    # ... a plain run (no --full): nothing after the timed steps, the rccl block names the collective without timing it
+    assert d["step_ms_spread"] is None and d["rccl"]["backend"] == "gloo" and d["rccl"]["world_size"] == 2 and "per_rank_ms_with_gather" not in d["rccl"]
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "1", "--global-batch", "9"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0                    # 9 pairs do not split over 2 ranks
 
