@@ -6,7 +6,13 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import Optional, Tuple
+
+# torch wheels bundle their own libamdhip64.so (SONAME libamdhip64.so.7).  If OUR library were dlopen'ed first it would
+# pull /opt/rocm's copy and the process would end up with TWO HIP runtimes (ours then sees no device: hipErrorNoDevice at
+# the first launch).  Importing torch first makes the loader resolve our DT_NEEDED libamdhip64.so.7 to the copy torch
+# already loaded.
+import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OPENGLUE_AMD_LIB") or os.path.join(HERE, "lib", "libopenglue_amd.so")   # override: A/B builds
@@ -169,11 +175,6 @@ def load() -> C.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    # torch wheels bundle their own libamdhip64.so (SONAME libamdhip64.so.7).  If OUR library were
-    # dlopen'ed first it would pull /opt/rocm's copy and the process would end up with TWO HIP runtimes
-    # (ours then sees no device: hipErrorNoDevice at the first launch).  Importing torch first makes the
-    # loader resolve our DT_NEEDED libamdhip64.so.7 to the copy torch already loaded.
-    import torch  # noqa: F401
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             f"{LIB_PATH} not found: build it with `python -m openglue_amd.build` "
@@ -194,3 +195,39 @@ def check(rc: int, what: str) -> None:
     if rc < 0:
         raise RuntimeError(f"{what}: {_ERRORS.get(rc, rc)}")
     raise RuntimeError(f"{what}: HIP error {rc} at kernel launch")
+
+
+STREAM = object()           # in the argument list of call(): where the entry point takes its hipStream_t
+
+
+def call(name: str, dev: torch.device, *args) -> None:
+    """Launch the entry point `name` with `dev` as the current device and the current stream of `dev` in place of STREAM; a
+    failure is reported under `name`.  The C side never sets the device: it launches on the stream it is handed, in whatever
+    device context the caller left (and og_sinkhorn sizes its resident launch from the current device's properties)."""
+    fn = getattr(load(), name)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = fn(*[stream if a is STREAM else a for a in args])
+    check(rc, name)
+
+
+def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
+    return None if t is None else t.data_ptr()
+
+
+def gpu_tensor(t, name: str, dtype=torch.float32, convert: bool = False) -> torch.Tensor:
+    """`t` as a contiguous `dtype` tensor on the GPU.  Anything that is not a GPU tensor is refused; another dtype is converted
+    (detached) with `convert`, refused without."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name}: expected a tensor on the GPU; openglue_amd has no CPU path")
+    if convert:
+        return t.detach().to(dtype).contiguous()
+    if t.dtype != dtype:
+        raise RuntimeError(f"{name}: expected {dtype}, got {t.dtype}")
+    return t.contiguous()
+
+
+def workspace(nbytes: int, dev: torch.device) -> Tuple[torch.Tensor, int]:
+    """Device scratch of `nbytes` -> (the tensor that owns it, a 256-byte aligned address inside it)."""
+    ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256

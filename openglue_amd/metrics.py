@@ -23,7 +23,7 @@ Where the pose estimate deliberately differs from the reference's cv2.findEssent
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence
+from typing import Dict, Sequence
 
 import torch
 
@@ -32,26 +32,11 @@ from . import _lib
 _TKEYS = ("K0", "K1", "R", "T")
 
 
-def _stream(dev: torch.device) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _gpu(t, name, dtype=torch.float32) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: expected a tensor on the GPU; openglue_amd has no CPU path")
-    return t.detach().to(dtype).contiguous()
-
-
-def _workspace(nbytes: int, dev: torch.device):
-    ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
-    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
-
-
 def _batch(keypoints0, keypoints1, matches0, transformation, num_keypoints0):
     """Validate and convert one SuperGlue.match-shaped batch -> (B, M, N, tensors kept alive)."""
-    k0 = _gpu(keypoints0, "keypoints0")
-    k1 = _gpu(keypoints1, "keypoints1")
-    m0 = _gpu(matches0, "matches0", torch.int64)
+    k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
+    k1 = _lib.gpu_tensor(keypoints1, "keypoints1", convert=True)
+    m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
     if k0.dim() != 3 or k0.shape[2] != 2 or k1.dim() != 3 or k1.shape[2] != 2 or k1.shape[0] != k0.shape[0]:
         raise ValueError("keypoints0 / keypoints1 must be [B, M, 2] / [B, N, 2]")
     B, M, N = k0.shape[0], k0.shape[1], k1.shape[1]
@@ -59,21 +44,17 @@ def _batch(keypoints0, keypoints1, matches0, transformation, num_keypoints0):
         raise ValueError(f"matches0 must be [B, M] = [{B}, {M}], got {list(m0.shape)}")
     t = {}
     for key in _TKEYS:
-        v = _gpu(transformation[key], f"transformation['{key}']")
+        v = _lib.gpu_tensor(transformation[key], f"transformation['{key}']", convert=True)
         want = (B, 3) if key == "T" else (B, 3, 3)
         if tuple(v.shape) != want:
             raise ValueError(f"transformation['{key}'] must be {list(want)}, got {list(v.shape)}")
         t[key] = v
     nk = None
     if num_keypoints0 is not None:
-        nk = _gpu(num_keypoints0, "num_keypoints0", torch.int32)
+        nk = _lib.gpu_tensor(num_keypoints0, "num_keypoints0", torch.int32, convert=True)
         if tuple(nk.shape) != (B,):
             raise ValueError(f"num_keypoints0 must be [B] = [{B}]")
     return B, M, N, k0, k1, m0, t, nk
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
 
 
 def epipolar_precision(keypoints0, keypoints1, matches0, transformation, num_keypoints0=None, threshold: float = 5e-4
@@ -81,15 +62,12 @@ def epipolar_precision(keypoints0, keypoints1, matches0, transformation, num_key
     """utils/metrics.py:17-46 for a batch -> {'precision' [B], 'matching_score' [B] fp32, 'num_correct' [B] int32}."""
     B, M, N, k0, k1, m0, t, nk = _batch(keypoints0, keypoints1, matches0, transformation, num_keypoints0)
     dev = k0.device
-    lib = _lib.load()
     prec = torch.empty(B, device=dev, dtype=torch.float32)
     score = torch.empty(B, device=dev, dtype=torch.float32)
     correct = torch.empty(B, device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        rc = lib.og_epipolar_precision(B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _ptr(nk), t["K0"].data_ptr(),
-                                       t["K1"].data_ptr(), t["R"].data_ptr(), t["T"].data_ptr(), float(threshold),
-                                       prec.data_ptr(), score.data_ptr(), correct.data_ptr(), _stream(dev))
-    _lib.check(rc, "og_epipolar_precision")
+    _lib.call("og_epipolar_precision", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), t["K0"].data_ptr(),
+              t["K1"].data_ptr(), t["R"].data_ptr(), t["T"].data_ptr(), float(threshold),
+              prec.data_ptr(), score.data_ptr(), correct.data_ptr(), _lib.STREAM)
     return {"precision": prec, "matching_score": score, "num_correct": correct}
 
 
@@ -108,44 +86,39 @@ def relative_pose(keypoints0, keypoints1, matches0, transformation, ransac_inlie
     nbytes = lib.og_relative_pose_workspace_bytes(B, M, hypotheses)
     if nbytes == 0:
         raise ValueError("unsupported relative_pose sizes")
-    ws, wp = _workspace(nbytes, dev)
+    ws, wp = _lib.workspace(nbytes, dev)
     err = torch.empty(B, device=dev, dtype=torch.float32)
     Rp = torch.empty(B, 3, 3, device=dev, dtype=torch.float32)
     tp = torch.empty(B, 3, device=dev, dtype=torch.float32)
     inl = torch.empty(B, max(M, 1), device=dev, dtype=torch.uint8)
     ninl = torch.empty(B, device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        rc = lib.og_relative_pose(B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _ptr(nk), t["K0"].data_ptr(),
-                                  t["K1"].data_ptr(), t["R"].data_ptr(), t["T"].data_ptr(), float(ransac_inliers_threshold),
-                                  hypotheses, int(seed) & (2 ** 64 - 1), int(pair_offset), err.data_ptr(), Rp.data_ptr(),
-                                  tp.data_ptr(), inl.data_ptr(), ninl.data_ptr(), wp, _stream(dev))
-    _lib.check(rc, "og_relative_pose")
+    _lib.call("og_relative_pose", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), t["K0"].data_ptr(),
+              t["K1"].data_ptr(), t["R"].data_ptr(), t["T"].data_ptr(), float(ransac_inliers_threshold),
+              hypotheses, int(seed) & (2 ** 64 - 1), int(pair_offset), err.data_ptr(), Rp.data_ptr(),
+              tp.data_ptr(), inl.data_ptr(), ninl.data_ptr(), wp, _lib.STREAM)
     return {"R": Rp, "t": tp, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "error": err}
 
 
 def essential_5pt(x0: torch.Tensor, x1: torch.Tensor):
     """The five-point minimal solver on its own: x0, x1 [count, 5, 2] calibrated correspondences (x1^T E x0 = 0) ->
     (E [count, 10, 3, 3] float64, unit Frobenius norm; num_solutions [count] int32).  Entries past num_solutions are undefined."""
-    a = _gpu(x0, "x0", torch.float64)
-    b = _gpu(x1, "x1", torch.float64)
+    a = _lib.gpu_tensor(x0, "x0", torch.float64, convert=True)
+    b = _lib.gpu_tensor(x1, "x1", torch.float64, convert=True)
     if a.dim() != 3 or a.shape[1:] != (5, 2) or b.shape != a.shape or a.shape[0] == 0:
         raise ValueError("x0 / x1 must both be [count, 5, 2] with count > 0")
     count = a.shape[0]
     dev = a.device
-    lib = _lib.load()
     E = torch.empty(count, 10, 3, 3, device=dev, dtype=torch.float64)
     ns = torch.empty(count, device=dev, dtype=torch.int32)
-    with torch.cuda.device(dev):
-        rc = lib.og_essential_5pt(count, a.data_ptr(), b.data_ptr(), E.data_ptr(), ns.data_ptr(), _stream(dev))
-    _lib.check(rc, "og_essential_5pt")
+    _lib.call("og_essential_5pt", dev, count, a.data_ptr(), b.data_ptr(), E.data_ptr(), ns.data_ptr(), _lib.STREAM)
     return E, ns
 
 
 def _single_pair(matched_kpts0, matched_kpts1, transformation, num_detected_kpts=None):
     """One pair as the reference passes it (compacted matches, a per-pair transformation) -> a B = 1 batch.  With
     num_detected_kpts the keypoints are padded to that many rows with -1 matches, so that matching_score divides by it."""
-    k0 = _gpu(matched_kpts0, "matched_kpts0")
-    k1 = _gpu(matched_kpts1, "matched_kpts1")
+    k0 = _lib.gpu_tensor(matched_kpts0, "matched_kpts0", convert=True)
+    k1 = _lib.gpu_tensor(matched_kpts1, "matched_kpts1", convert=True)
     if k0.dim() != 2 or k0.shape[1] != 2 or tuple(k1.shape) != tuple(k0.shape):
         raise ValueError("matched_kpts0 / matched_kpts1 must both be [K, 2]")
     K = k0.shape[0]
@@ -155,7 +128,7 @@ def _single_pair(matched_kpts0, matched_kpts1, transformation, num_detected_kpts
     kp0[0, :K] = k0
     m0 = torch.full((1, M), -1, device=dev, dtype=torch.int64)
     m0[0, :K] = torch.arange(K, device=dev)
-    tr = {key: _gpu(transformation[key], f"transformation['{key}']").unsqueeze(0) for key in _TKEYS}
+    tr = {key: _lib.gpu_tensor(transformation[key], f"transformation['{key}']", convert=True).unsqueeze(0) for key in _TKEYS}
     nk = None if num_detected_kpts is None else torch.full((1,), int(num_detected_kpts), device=dev, dtype=torch.int32)
     return kp0, k1.unsqueeze(0), m0, tr, nk
 

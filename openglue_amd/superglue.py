@@ -407,23 +407,21 @@ class SuperGlue(nn.Module):
             ptr = lambda k: out[k].data_ptr() if k in out else None
             o = _lib.og_outputs(ptr("scores"), ptr("context_descriptors0"), ptr("context_descriptors1"),
                                 ptr("matches0"), ptr("matching_scores0"), ptr("matches1"), ptr("matching_scores1"))
-            st = torch.cuda.current_stream(dev).cuda_stream
             if _tap == "encoder":    # the keypoint-encoder stage alone (og_keypoint_encoder): nothing else runs, nothing else is written
                 out = {"_tap_x": torch.empty(B * (m + n), D, device=dev, dtype=torch.float32)}
-                rc = lib.og_keypoint_encoder(C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), out["_tap_x"].data_ptr(), st)
-                _lib.check(rc, "og_keypoint_encoder")
+                _lib.call("og_keypoint_encoder", dev, C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), out["_tap_x"].data_ptr(),
+                          _lib.STREAM)
                 out["_bmn"] = (B, m, n)
                 return out
             if _tap is not None:     # per-stage parity tests: the residual stream at one stage boundary (og_forward_tap)
                 out["_tap_x"] = torch.empty(B * (m + n), D, device=dev, dtype=torch.float32)
-                rc = lib.og_forward_tap(C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), C.byref(o), st, int(_tap),
-                                        out["_tap_x"].data_ptr())
+                _lib.call("og_forward_tap", dev, C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), C.byref(o), _lib.STREAM,
+                          int(_tap), out["_tap_x"].data_ptr())
             elif _profile is None:
-                rc = lib.og_forward(C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), C.byref(o), st)
+                _lib.call("og_forward", dev, C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), C.byref(o), _lib.STREAM)
             else:      # bench.py: per-kernel-class HIP-event times (synchronises the stream)
-                rc = lib.og_forward_profiled(C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), C.byref(o), st,
-                                             _profile[0], _profile[1])
-            _lib.check(rc, "og_forward")
+                _lib.call("og_forward_profiled", dev, C.byref(shape), C.byref(inp), packed.data_ptr(), ws.data_ptr(), C.byref(o), _lib.STREAM,
+                          _profile[0], _profile[1])
         return out
 
     @torch.no_grad()
@@ -540,13 +538,12 @@ class SuperGlue(nn.Module):
                                     m1.data_ptr() if both_sides else None, s1.data_ptr() if both_sides else None)
                 a0 = (C.c_int32 * B)(*l0)
                 a1 = (C.c_int32 * B)(*l1)
-                st = torch.cuda.current_stream(dev).cuda_stream
                 if _profile is None:
-                    rc = lib.og_forward_ragged(C.byref(shape), a0, a1, wh0, wh1, C.byref(inp), pk.data_ptr(), ws.data_ptr(), C.byref(o), st)
+                    _lib.call("og_forward_ragged", dev, C.byref(shape), a0, a1, wh0, wh1, C.byref(inp), pk.data_ptr(), ws.data_ptr(), C.byref(o),
+                              _lib.STREAM)
                 else:
-                    rc = lib.og_forward_ragged_profiled(C.byref(shape), a0, a1, wh0, wh1, C.byref(inp), pk.data_ptr(), ws.data_ptr(),
-                                                        C.byref(o), st, _profile[0], _profile[1])
-                _lib.check(rc, "og_forward_ragged")
+                    _lib.call("og_forward_ragged_profiled", dev, C.byref(shape), a0, a1, wh0, wh1, C.byref(inp), pk.data_ptr(), ws.data_ptr(),
+                              C.byref(o), _lib.STREAM, _profile[0], _profile[1])
             so = o0 = o1 = 0
             for a, b in zip(l0, l1):
                 r = {"scores": scores[so:so + (a + 1) * (b + 1)].view(a + 1, b + 1), "matches0": m0[o0:o0 + a],

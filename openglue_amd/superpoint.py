@@ -126,10 +126,8 @@ class SuperPointNet(nn.Module):
         heat = torch.empty(B, Hc * 8, Wc * 8, device=dev, dtype=torch.float32)
         desc = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
         ws = workspace if workspace is not None else self._workspace(B, H, W, dev)
-        lib = _lib.load()
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.og_superpoint_dense(B, H, W, img.data_ptr(), packed.data_ptr(), heat.data_ptr(), desc.data_ptr(),
-                                           ws.data_ptr(), st), "og_superpoint_dense")
+        _lib.call("og_superpoint_dense", dev, B, H, W, img.data_ptr(), packed.data_ptr(), heat.data_ptr(), desc.data_ptr(),
+                  ws.data_ptr(), _lib.STREAM)
         return heat, desc
 
     def _workspace(self, B, H, W, dev) -> torch.Tensor:
@@ -142,16 +140,13 @@ class SuperPointNet(nn.Module):
         """heatmap -> (counts [2B] int32 on the device, sel_idx [B, cap], sel_score [B, cap], cap)."""
         B, Hh, Wh = heat.shape
         dev = heat.device
-        lib = _lib.load()
         k = int(self.max_keypoints)
-        cap = lib.og_superpoint_capacity(Hh, Wh, k)
+        cap = _lib.load().og_superpoint_capacity(Hh, Wh, k)
         counts = torch.empty(2 * B, device=dev, dtype=torch.int32)
         sidx = torch.empty(B, cap, device=dev, dtype=torch.int32)
         sscore = torch.empty(B, cap, device=dev, dtype=torch.float32)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.og_superpoint_detect(B, Hh, Wh, int(self.nms_kernel), int(self.remove_borders_size), float(self.keypoint_threshold),
-                                            k, heat.data_ptr(), counts.data_ptr(), sidx.data_ptr(), sscore.data_ptr(), cap,
-                                            workspace.data_ptr(), st), "og_superpoint_detect")
+        _lib.call("og_superpoint_detect", dev, B, Hh, Wh, int(self.nms_kernel), int(self.remove_borders_size), float(self.keypoint_threshold),
+                  k, heat.data_ptr(), counts.data_ptr(), sidx.data_ptr(), sscore.data_ptr(), cap, workspace.data_ptr(), _lib.STREAM)
         return counts, sidx, sscore, cap
 
     def describe(self, n: int, sidx: torch.Tensor, sscore: torch.Tensor, desc: torch.Tensor):
@@ -160,10 +155,8 @@ class SuperPointNet(nn.Module):
         lafs = torch.empty(B, n, 2, 3, device=dev, dtype=torch.float32)
         scores = torch.empty(B, n, device=dev, dtype=torch.float32)
         descriptors = torch.empty(B, n, 256, device=dev, dtype=torch.float32)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(_lib.load().og_superpoint_describe(B, Hc, Wc, n, sidx.data_ptr(), sscore.data_ptr(), sidx.shape[1], desc.data_ptr(),
-                                                      lafs.data_ptr(), scores.data_ptr(), descriptors.data_ptr(), st),
-                   "og_superpoint_describe")
+        _lib.call("og_superpoint_describe", dev, B, Hc, Wc, n, sidx.data_ptr(), sscore.data_ptr(), sidx.shape[1], desc.data_ptr(),
+                  lafs.data_ptr(), scores.data_ptr(), descriptors.data_ptr(), _lib.STREAM)
         return lafs, scores, descriptors
 
     @torch.no_grad()

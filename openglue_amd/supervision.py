@@ -36,21 +36,6 @@ IGNORE_INDEX = -2
 _TRANSFORMS = {"perspective": 0, "3d_reprojection": 1}
 
 
-def _stream(dev: torch.device) -> int:
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _gpu(t, name, dtype=torch.float32) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise RuntimeError(f"{name}: expected a tensor on the GPU; openglue_amd has no CPU path")
-    return t.detach().to(dtype).contiguous()
-
-
-def _workspace(nbytes: int, dev: torch.device) -> Tuple[torch.Tensor, int]:
-    ws = torch.empty(nbytes + 256, device=dev, dtype=torch.uint8)
-    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
-
-
 def generate_gt_matches(data: Dict[str, Any], features0: Dict[str, torch.Tensor], features1: Dict[str, torch.Tensor],
                         positive_threshold: float, negative_threshold: Optional[float] = None, apply_thresholds: bool = False
                         ) -> Tuple[Optional[Dict[str, Any]], Optional[Dict[str, torch.Tensor]]]:
@@ -64,8 +49,8 @@ def generate_gt_matches(data: Dict[str, Any], features0: Dict[str, torch.Tensor]
     ttype = transformation["type"][0]
     if ttype not in _TRANSFORMS:
         raise ValueError(f"Unknown transformation type {ttype}.")
-    kpts0 = _gpu(features0["keypoints"], "features0['keypoints']")
-    kpts1 = _gpu(features1["keypoints"], "features1['keypoints']")
+    kpts0 = _lib.gpu_tensor(features0["keypoints"], "features0['keypoints']", convert=True)
+    kpts1 = _lib.gpu_tensor(features1["keypoints"], "features1['keypoints']", convert=True)
     B, M = kpts0.shape[:2]
     N = kpts1.shape[1]
     if M == 0 or N == 0:
@@ -77,7 +62,7 @@ def generate_gt_matches(data: Dict[str, Any], features0: Dict[str, torch.Tensor]
     keep = []
 
     def mat(name, shape):
-        t = _gpu(transformation[name], f"transformation['{name}']")
+        t = _lib.gpu_tensor(transformation[name], f"transformation['{name}']", convert=True)
         if tuple(t.shape) != shape:
             raise ValueError(f"transformation['{name}'] must be {list(shape)}, got {list(t.shape)}")
         keep.append(t)
@@ -91,7 +76,7 @@ def generate_gt_matches(data: Dict[str, Any], features0: Dict[str, torch.Tensor]
         K0, K1, R, T = mat("K0", (B, 3, 3)), mat("K1", (B, 3, 3)), mat("R", (B, 3, 3)), mat("T", (B, 3))
         ptrs = []
         for side, cnt in ((0, M), (1, N)):
-            d = _gpu(transformation[f"depth{side}"], f"transformation['depth{side}']")
+            d = _lib.gpu_tensor(transformation[f"depth{side}"], f"transformation['depth{side}']", convert=True)
             if d.dim() == 2:
                 if tuple(d.shape) != (B, cnt):
                     raise ValueError(f"per-keypoint depth{side} must be [B, {cnt}]")
@@ -105,13 +90,11 @@ def generate_gt_matches(data: Dict[str, Any], features0: Dict[str, torch.Tensor]
     gt0 = torch.empty(B, M, device=dev, dtype=torch.int64)
     gt1 = torch.empty(B, N, device=dev, dtype=torch.int64)
     status = torch.empty(1, device=dev, dtype=torch.int32)
-    ws, wp = _workspace(lib.og_gt_matches_workspace_bytes(B, M, N), dev)
-    with torch.cuda.device(dev):
-        rc = lib.og_gt_matches(B, M, N, kpts0.data_ptr(), kpts1.data_ptr(), _TRANSFORMS[ttype], H, K0, K1, R, T,
-                               dp0, dims[0], dims[1], dp1, dims[2], dims[3], int(bool(apply_thresholds)),
-                               float(positive_threshold), float(negative_threshold), gt0.data_ptr(), gt1.data_ptr(),
-                               status.data_ptr(), wp, _stream(dev))
-    _lib.check(rc, "og_gt_matches")
+    ws, wp = _lib.workspace(lib.og_gt_matches_workspace_bytes(B, M, N), dev)
+    _lib.call("og_gt_matches", dev, B, M, N, kpts0.data_ptr(), kpts1.data_ptr(), _TRANSFORMS[ttype], H, K0, K1, R, T,
+              dp0, dims[0], dims[1], dp1, dims[2], dims[3], int(bool(apply_thresholds)),
+              float(positive_threshold), float(negative_threshold), gt0.data_ptr(), gt1.data_ptr(),
+              status.data_ptr(), wp, _lib.STREAM)
     if dims[0] or dims[2]:
         bad = int(status.item())
         if bad:
@@ -133,25 +116,24 @@ class _Criterion(torch.autograd.Function):
         dev = scores.device
         B, M1, N1 = scores.shape
         M, N = M1 - 1, N1 - 1
-        S = _gpu(scores, "scores")
-        g0, g1 = _gpu(gt0, "gt_matches0", torch.int64), _gpu(gt1, "gt_matches1", torch.int64)
+        S = _lib.gpu_tensor(scores, "scores", convert=True)
+        g0 = _lib.gpu_tensor(gt0, "gt_matches0", torch.int64, convert=True)
+        g1 = _lib.gpu_tensor(gt1, "gt_matches1", torch.int64, convert=True)
         if g0.shape != (B, M) or g1.shape != (B, N):
             raise ValueError("gt_matches0 / gt_matches1 must be [B, M] / [B, N] for scores [B, M+1, N+1]")
         on = margin is not None
         D = 0
         a = b = None
         if on:
-            a, b = _gpu(desc0, "context_descriptors0"), _gpu(desc1, "context_descriptors1")
+            a = _lib.gpu_tensor(desc0, "context_descriptors0", convert=True)
+            b = _lib.gpu_tensor(desc1, "context_descriptors1", convert=True)
             D = a.shape[1]
             if a.shape != (B, D, M) or b.shape != (B, D, N):
                 raise ValueError("context_descriptors0 / 1 must be [B, D, M] / [B, D, N]")
-        ws, wp = _workspace(lib.og_criterion_workspace_bytes(B, M, N, int(on)), dev)
+        ws, wp = _lib.workspace(lib.og_criterion_workspace_bytes(B, M, N, int(on)), dev)
         out = torch.empty(2, device=dev, dtype=torch.float32)
-        p = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib.og_criterion_forward(S.data_ptr(), g0.data_ptr(), g1.data_ptr(), p(a), p(b), B, M, N, D, int(on),
-                                          float(margin) if on else 0.0, out.data_ptr(), wp, _stream(dev))
-        _lib.check(rc, "og_criterion_forward")
+        _lib.call("og_criterion_forward", dev, S.data_ptr(), g0.data_ptr(), g1.data_ptr(), _lib.ptr(a), _lib.ptr(b), B, M, N, D, int(on),
+                  float(margin) if on else 0.0, out.data_ptr(), wp, _lib.STREAM)
         ctx.keep = (ws, wp, g0, g1, a, b)
         ctx.args = (B, M, N, D, on, float(margin) if on else 0.0)
         ctx.meta = (scores.dtype, desc0.dtype if on else None, desc1.dtype if on else None)
@@ -159,7 +141,6 @@ class _Criterion(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_loss, g_metric):
-        lib = _lib.load()
         ws, wp, g0, g1, a, b = ctx.keep
         B, M, N, D, on, margin = ctx.args
         dev = g0.device
@@ -173,11 +154,8 @@ class _Criterion(torch.autograd.Function):
         gS = torch.empty(B, M + 1, N + 1, device=dev, dtype=torch.float32) if need_s else None
         gA = torch.empty(B, D, M, device=dev, dtype=torch.float32) if need_d else None
         gB = torch.empty(B, D, N, device=dev, dtype=torch.float32) if need_d else None
-        p = lambda t: None if t is None else t.data_ptr()
-        with torch.cuda.device(dev):
-            rc = lib.og_criterion_backward(g0.data_ptr(), g1.data_ptr(), p(a), p(b), B, M, N, D, int(on), margin, gl.data_ptr(),
-                                           wp, p(gS), p(gA), p(gB), _stream(dev))
-        _lib.check(rc, "og_criterion_backward")
+        _lib.call("og_criterion_backward", dev, g0.data_ptr(), g1.data_ptr(), _lib.ptr(a), _lib.ptr(b), B, M, N, D, int(on), margin,
+                  gl.data_ptr(), wp, _lib.ptr(gS), _lib.ptr(gA), _lib.ptr(gB), _lib.STREAM)
         sd, d0d, d1d = ctx.meta
         return (gS.to(sd) if gS is not None else None, gA.to(d0d) if gA is not None else None,
                 gB.to(d1d) if gB is not None else None, None, None, None)

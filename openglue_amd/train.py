@@ -12,24 +12,22 @@ Conv1d -> ReLU -> BatchNorm1d with batch statistics and running-statistics updat
 `feed_forward_train_autograd` adds the backward of that block (1x1 conv: dX, dW, db on the exact-fp32 GEMM; ReLU + train-mode
 BatchNorm: og_batchnorm_train_backward), so the keypoint-encoder MLP / a message MLP can be trained end to end on HIP kernels.
 
-`superglue_forward_train` (below) wires them -- plus `Conv1x1`, `SoftmaxAttention` (materialised attention matrix, batched exact-fp32
-GEMMs, row-softmax forward / backward kernels) and `MatchingScores` -- into the whole training-mode forward of the reference
+`superglue_forward_train` (below) wires them -- plus `Conv1x1`, `SoftmaxAttention` / `ProjectedAttention` (flash forward and backward
+kernels at head sizes 16 / 32 / 64; other head sizes materialise the attention matrix: batched exact-fp32 GEMMs, row-softmax forward /
+backward kernels) and `MatchingScores` -- into the whole training-mode forward of the reference
 (superglue.py:29-72): `SuperGlue(config).train()(data)` returns tensors whose `loss.backward()` reaches every parameter.  `LinearAttentionCore`
 (+ `linear_attention_elu_train`, `favor_relu_attention_train`) is the O(N) attention of attention.py:22-40 / :86-95 under autograd, the
 Siren encoder (models/utils.py:32-45) runs through `Conv1x1` + sin(30 x).
 """
 from __future__ import annotations
 
-import os as _os
-
-import torch
+import os
+import warnings
 from typing import Optional
 
-from . import _lib
+import torch
 
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
+from . import _lib, ops
 
 
 class SinkhornOT(torch.autograd.Function):
@@ -50,30 +48,26 @@ class SinkhornOT(torch.autograd.Function):
         nbytes = lib.og_sinkhorn_train_workspace_bytes(B, m, n, int(num_iters))
         if nbytes == 0:
             raise RuntimeError("og_sinkhorn_train_workspace_bytes: unsupported shape (n <= 4159, num_iters >= 1)")
-        ws = torch.empty(nbytes + 256, device=S.device, dtype=torch.uint8)
-        off = (-ws.data_ptr()) % 256
+        ws, wp = _lib.workspace(nbytes, S.device)
         scores = torch.empty(B, m + 1, n + 1, device=S.device, dtype=torch.float32)
         # the learnable dustbin score is read ON the device (ABI v6): no float(tensor) here, the host never waits for the GPU mid-step
         zdev = dustbin_score.detach().to(device=S.device, dtype=torch.float32).reshape(1).contiguous()
-        with torch.cuda.device(S.device):
-            _lib.check(lib.og_sinkhorn_train_forward(Sp.data_ptr(), lds, 0.0, zdev.data_ptr(), B, m, n, int(num_iters), float(reg),
-                                                     scores.data_ptr(), ws.data_ptr() + off, _stream(S)), "og_sinkhorn_train_forward")
+        _lib.call("og_sinkhorn_train_forward", S.device, Sp.data_ptr(), lds, 0.0, zdev.data_ptr(), B, m, n, int(num_iters), float(reg),
+                  scores.data_ptr(), wp, _lib.STREAM)
         ctx.save_for_backward(Sp, zdev)
-        ctx.ws, ctx.off, ctx.args = ws, off, (B, m, n, lds, int(num_iters), float(reg))
+        ctx.ws, ctx.wp, ctx.args = ws, wp, (B, m, n, lds, int(num_iters), float(reg))       # ws owns the memory behind wp
         ctx.dustbin_meta = (dustbin_score.dtype, dustbin_score.shape)
         return scores
 
     @staticmethod
     def backward(ctx, grad_scores: torch.Tensor):
-        lib = _lib.load()
         Sp, zdev = ctx.saved_tensors
         B, m, n, lds, iters, reg = ctx.args
         g = grad_scores.detach().to(torch.float32).contiguous()
         dS = torch.empty(B, m, lds, device=Sp.device, dtype=torch.float32)
         dz = torch.zeros(1, device=Sp.device, dtype=torch.float32)
-        with torch.cuda.device(Sp.device):
-            _lib.check(lib.og_sinkhorn_backward(Sp.data_ptr(), lds, 0.0, zdev.data_ptr(), B, m, n, iters, reg, g.data_ptr(), ctx.ws.data_ptr() + ctx.off,
-                                                dS.data_ptr(), lds, dz.data_ptr(), _stream(Sp)), "og_sinkhorn_backward")
+        _lib.call("og_sinkhorn_backward", Sp.device, Sp.data_ptr(), lds, 0.0, zdev.data_ptr(), B, m, n, iters, reg, g.data_ptr(), ctx.wp,
+                  dS.data_ptr(), lds, dz.data_ptr(), _lib.STREAM)
         dtype, shape = ctx.dustbin_meta
         return dS[:, :, :n], dz.reshape(shape).to(dtype), None, None
 
@@ -104,12 +98,15 @@ def batch_norm_train(x: torch.Tensor, weight, bias, running_mean, running_var, m
     y = torch.empty(T, C, device=x.device, dtype=torch.float32) if out is None else out          # out: a [T, C] row slice of a larger buffer
     mean = torch.empty(C, device=x.device, dtype=torch.float32) if return_stats else None
     invstd = torch.empty(C, device=x.device, dtype=torch.float32) if return_stats else None
-    p = lambda t: None if t is None else t.data_ptr()       # noqa: E731
-    with torch.cuda.device(x.device):
-        _lib.check(lib.og_batchnorm_train_forward(x.data_ptr(), x.stride(0), T, C, p(weight), p(bias), float(eps), float(momentum),
-                                                  p(running_mean), p(running_var), y.data_ptr(), y.stride(0), p(mean), p(invstd),
-                                                  ws.data_ptr(), _stream(x)), "og_batchnorm_train_forward")
+    _lib.call("og_batchnorm_train_forward", x.device, x.data_ptr(), x.stride(0), T, C, _lib.ptr(weight), _lib.ptr(bias), float(eps),
+              float(momentum), _lib.ptr(running_mean), _lib.ptr(running_var), y.data_ptr(), y.stride(0), _lib.ptr(mean), _lib.ptr(invstd),
+              ws.data_ptr(), _lib.STREAM)
     return (y, mean, invstd) if return_stats else y
+
+
+def _w2d(w: torch.Tensor) -> torch.Tensor:
+    """Conv1d(kernel_size=1) weight [out, in, 1] (or already [out, in]) -> the [out, in] view the GEMMs take."""
+    return w.reshape(w.shape[0], w.shape[1])
 
 
 def feed_forward_train(x: torch.Tensor, state_dict, prefix: str = "", momentum: float = 0.1) -> torch.Tensor:
@@ -117,11 +114,9 @@ def feed_forward_train(x: torch.Tensor, state_dict, prefix: str = "", momentum: 
     the exact-fp32 MFMA GEMM with fused bias + ReLU (og_gemm_nt), then train-mode BatchNorm (og_batchnorm_train_forward: batch
     statistics, the running statistics inside `state_dict` are updated in place), then the last 1x1 conv.  Parameter names are
     the nn.Sequential ones: `{prefix}{3i}.weight|bias` (Conv1d, weight [out, in, 1]), `{prefix}{3i+2}.*` (BatchNorm1d)."""
-    from . import ops
     n_conv = len({k for k in state_dict if k.startswith(prefix) and k.endswith(".weight") and state_dict[k].dim() == 3})
     for i in range(n_conv):
-        w = state_dict[f"{prefix}{3 * i}.weight"]
-        x = ops.gemm_nt(x, w.reshape(w.shape[0], w.shape[1]).contiguous(), state_dict[f"{prefix}{3 * i}.bias"], relu=i + 1 < n_conv)
+        x = ops.gemm_nt(x, _w2d(state_dict[f"{prefix}{3 * i}.weight"]).contiguous(), state_dict[f"{prefix}{3 * i}.bias"], relu=i + 1 < n_conv)
         if i + 1 < n_conv:
             bn = f"{prefix}{3 * i + 2}"
             x = batch_norm_train(x, state_dict[bn + ".weight"], state_dict[bn + ".bias"], state_dict[bn + ".running_mean"],
@@ -137,52 +132,10 @@ def _ws(x: torch.Tensor, rows: int, C: int) -> torch.Tensor:
     return torch.empty(max(n, 256), device=x.device, dtype=torch.uint8)
 
 
-def _transpose_pad(x: torch.Tensor, mult: int = 4) -> torch.Tensor:
-    """[R, C] -> [C, round_up(R, mult)] (zero tail): both operands of the weight-gradient GEMM must be K-contiguous, K = R
-    (mult = 32: the contraction length the split-f16 kernel needs)."""
-    lib = _lib.load()
-    R, C = x.shape
-    R4 = (R + mult - 1) // mult * mult
-    out = torch.zeros(C, R4, device=x.device, dtype=torch.float32) if R4 != R else torch.empty(C, R, device=x.device, dtype=torch.float32)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.og_transpose_f32(x.data_ptr(), x.stride(0), R, C, out.data_ptr(), R4, _stream(x)), "og_transpose_f32")
-    return out
-
-
-# The 1x1 convs of the training step run on the exact-fp32 MFMA kernel by DEFAULT; OG_TRAIN_F16X3=1 moves them to the split-f16 3-pass
-# MFMA GEMM of the inference path (fp32-class accuracy at ~3x the rate: DESIGN.md 4.1) wherever the contraction length is a multiple of 32.  Gradients can be far below the binary16 range (an NLL averaged over thousands of keypoints: 1e-7 ... 1e-3), so
-# a gradient operand is multiplied by a power of two that brings its largest entry to ~2^11 before the (hi, lo) split and the product is
-# scaled back -- exact, and computed ON THE DEVICE (no host synchronisation).
-def _use_f16x3() -> bool:
-    import os
-    return os.environ.get("OG_TRAIN_F16X3", "0") != "0"
-
-
-def _pow2_to(t: torch.Tensor, target: float) -> torch.Tensor:
-    """0-d device tensor 2^k with amax(t) * 2^k in (target / 2, target]."""
-    amax = t.abs().amax().clamp_min(1e-30)
-    return torch.exp2(torch.floor(torch.log2(target / amax)))
-
-
-def _gemm_fast(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None, relu: bool = False, scale_a: bool = False) -> torch.Tensor:
-    """epilogue(a @ b^T), a [M, K], b [N, K] fp32: split-f16 kernel when K % 32 == 0 and N % 4 == 0, else the exact-fp32 kernel.
-    scale_a: `a` is a gradient (see above).  b (weights / activations, additionally x256 inside the kernel wrapper) is scaled DOWN only
-    when its largest entry would leave binary16."""
-    from . import ops
-    M, K = a.shape
-    N = b.shape[0]
-    if not (_use_f16x3() and K % 32 == 0 and N % 4 == 0 and K >= 32):
-        return ops.gemm_nt(a, b, bias, relu=relu)
-    sb = torch.clamp(_pow2_to(b, 64.0), max=1.0)                  # 256 * 64 = 2^14
-    sa = _pow2_to(a, 2048.0) if scale_a else torch.clamp(_pow2_to(a, 16384.0), max=1.0)
-    s = sa * sb
-    out = ops.gemm_nt_f16x3((a * sa).contiguous(), (b * sb).contiguous(), None if bias is None else (bias * s).contiguous(), relu=relu)
-    return out * (1.0 / s)
-
-
 def _env_int(name: str, default: int, lo: int = 1) -> int:
-    """An experiment knob from the environment: a malformed or out-of-range value falls back to the default with a warning (never an import error)."""
-    raw = _os.environ.get(name)
+    """An experiment knob from the environment (the one reader of every OG_TRAIN_* variable): a malformed or out-of-range value falls back
+    to the default with a warning (never an import error)."""
+    raw = os.environ.get(name)
     if raw is None:
         return default
     try:
@@ -190,7 +143,6 @@ def _env_int(name: str, default: int, lo: int = 1) -> int:
     except ValueError:
         v = None
     if v is None or v < lo:
-        import warnings
         warnings.warn(f"{name}={raw!r} ignored (expected an integer >= {lo}); using {default}", RuntimeWarning)
         return default
     return v
@@ -220,9 +172,7 @@ def _gemm_splitk(dz: torch.Tensor, x: torch.Tensor, with_colsum: bool = False):
     # padded rows plus two strided copies)
     dW = torch.empty(Cout, Cin, device=dz.device, dtype=torch.float32)
     db = torch.empty(Cout, device=dz.device, dtype=torch.float32) if with_colsum else None
-    with torch.cuda.device(dz.device):
-        _lib.check(_lib.load().og_splitk_reduce(part.data_ptr(), parts, Cout, ldc, Cin, dW.data_ptr(), None if db is None else db.data_ptr(),
-                                                _stream(dz)), "og_splitk_reduce")
+    _lib.call("og_splitk_reduce", dz.device, part.data_ptr(), parts, Cout, ldc, Cin, dW.data_ptr(), _lib.ptr(db), _lib.STREAM)
     return (dW, db) if with_colsum else dW
 
 
@@ -238,12 +188,9 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
 def _conv_backward(x: torch.Tensor, W: torch.Tensor, dz: torch.Tensor, need_dx: bool, need_dw: bool = True):
     """1x1 conv on token rows, z = x W^T + b:  dx = dz W,  dW = dz^T x,  db = column sums of dz -- all on HIP kernels.
     need_dw False (W is a buffer: the FAVOR projection): only dx."""
-    lib = _lib.load()
     T, Cout = dz.shape
     dx = None
-    if need_dx and _use_f16x3() and Cout % 32 == 0:                                              # (K = Cout must be a multiple of 32 on BOTH operands)
-        dx = _gemm_fast(dz, _transpose_pad(W, 32), scale_a=True)                                 # [T, Cout] x [Cin, Cout]^T
-    elif need_dx:                                                                                # dz [T, Cout] x W [Cout][Cin] as it lies (k-major B)
+    if need_dx:                                                                                  # dz [T, Cout] x W [Cout][Cin] as it lies (k-major B)
         Cin = W.shape[1]
         dx = torch.empty(T, Cin, device=dz.device, dtype=torch.float32)
         _gemm_km(dz.device, dz.data_ptr(), dz.stride(0), 0, 0, W.data_ptr(), W.stride(0), 0, dx.data_ptr(), Cin, 0, T, Cin, Cout, 1)
@@ -259,14 +206,51 @@ class Conv1x1(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W, b):
         ctx.save_for_backward(x, W)
-        return _gemm_fast(x.detach(), W.detach().contiguous(), b.detach())
+        return ops.gemm_nt(x.detach(), W.detach().contiguous(), b.detach())
 
     @staticmethod
     def backward(ctx, dy):
         x, W = ctx.saved_tensors
-        dx, dW, db = _conv_backward(x.detach(), W.detach().contiguous(), _rows(dy) if not _use_f16x3() else dy.detach().contiguous(),
-                                    ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        return dx, dW, db
+        return _conv_backward(x.detach(), W.detach().contiguous(), _rows(dy), ctx.needs_input_grad[0],
+                              ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+
+
+def _bn_forward_ranges(a, gamma, beta, running_mean, running_var, momentum, eps, splits):
+    """Train-mode BatchNorm of a [T, C] over the consecutive row ranges `splits` (None: all rows as one): batch statistics and one
+    running-statistics update per range, in order.  -> y, the ranges as a tuple, [mean, invstd of range 0, mean, invstd of range 1, ...]."""
+    splits = tuple(splits) if splits else (a.shape[0],)
+    if sum(splits) != a.shape[0]:
+        raise ValueError("splits must add up to the rows of x")
+    y = torch.empty_like(a)
+    stats, r0 = [], 0
+    for rows in splits:
+        _, mean, invstd = batch_norm_train(a[r0:r0 + rows], gamma.detach(), beta.detach(), running_mean, running_var, momentum, eps,
+                                           return_stats=True, out=y[r0:r0 + rows])
+        stats += [mean, invstd]
+        r0 += rows
+    return y, splits, stats
+
+
+def _bn_backward_ranges(a, dy, gamma, splits, stats):
+    """Backward of ReLU + _bn_forward_ranges: a [T, C] the ReLU output, dy [T, C] contiguous.  -> dz (gradient of the conv output),
+    dgamma, dbeta (summed in range order)."""
+    C = a.shape[1]
+    dz = torch.empty_like(a)
+    dgamma = dbeta = None
+    r0 = 0
+    for i, rows in enumerate(splits):
+        mean, invstd = stats[2 * i], stats[2 * i + 1]
+        dg = torch.empty(C, device=a.device, dtype=torch.float32)
+        dbt = torch.empty(C, device=a.device, dtype=torch.float32)
+        a_s, dy_s, dz_s = a[r0:r0 + rows], dy[r0:r0 + rows], dz[r0:r0 + rows]
+        ws = _ws(a, rows, C)
+        _lib.call("og_batchnorm_train_backward", a.device, a_s.data_ptr(), a_s.stride(0), dy_s.data_ptr(), dy_s.stride(0), rows, C,
+                  gamma.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1, dz_s.data_ptr(), dz_s.stride(0), dg.data_ptr(), dbt.data_ptr(),
+                  ws.data_ptr(), _lib.STREAM)
+        dgamma = dg if dgamma is None else dgamma + dg
+        dbeta = dbt if dbeta is None else dbeta + dbt
+        r0 += rows
+    return dz, dgamma, dbeta
 
 
 class ConvReluBNTrain(torch.autograd.Function):
@@ -278,110 +262,40 @@ class ConvReluBNTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, W, b, gamma, beta, running_mean, running_var, momentum, eps, splits=None):
-        a = _gemm_fast(x.detach(), W.detach().contiguous(), b.detach(), relu=True)
-        splits = tuple(splits) if splits else (a.shape[0],)
-        if sum(splits) != a.shape[0]:
-            raise ValueError("ConvReluBNTrain: splits must add up to the rows of x")
-        y = torch.empty_like(a)
-        stats, r0 = [], 0
-        for rows in splits:
-            _, mean, invstd = batch_norm_train(a[r0:r0 + rows], gamma.detach(), beta.detach(), running_mean, running_var, momentum, eps,
-                                               return_stats=True, out=y[r0:r0 + rows])
-            stats += [mean, invstd]
-            r0 += rows
+        a = ops.gemm_nt(x.detach(), W.detach().contiguous(), b.detach(), relu=True)
+        y, ctx.splits, stats = _bn_forward_ranges(a, gamma, beta, running_mean, running_var, momentum, eps, splits)
         ctx.save_for_backward(x, W, gamma, a, *stats)
-        ctx.splits = splits
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
         x, W, gamma, a, *stats = ctx.saved_tensors
-        T, C = a.shape
-        dy = dy.detach().contiguous()
-        dz = torch.empty_like(a)
-        dgamma = dbeta = None
-        r0 = 0
-        for i, rows in enumerate(ctx.splits):
-            mean, invstd = stats[2 * i], stats[2 * i + 1]
-            dg = torch.empty(C, device=a.device, dtype=torch.float32)
-            dbt = torch.empty(C, device=a.device, dtype=torch.float32)
-            a_s, dy_s, dz_s = a[r0:r0 + rows], dy[r0:r0 + rows], dz[r0:r0 + rows]
-            ws = _ws(a, rows, C)
-            with torch.cuda.device(a.device):
-                _lib.check(lib.og_batchnorm_train_backward(a_s.data_ptr(), a_s.stride(0), dy_s.data_ptr(), dy_s.stride(0), rows, C,
-                                                           gamma.detach().data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1, dz_s.data_ptr(),
-                                                           dz_s.stride(0), dg.data_ptr(), dbt.data_ptr(), ws.data_ptr(), _stream(a)),
-                           "og_batchnorm_train_backward")
-            dgamma = dg if dgamma is None else dgamma + dg
-            dbeta = dbt if dbeta is None else dbeta + dbt
-            r0 += rows
+        dz, dgamma, dbeta = _bn_backward_ranges(a, dy.detach().contiguous(), gamma.detach(), ctx.splits, stats)
         dx, dW, db = _conv_backward(x.detach(), W.detach().contiguous(), dz, ctx.needs_input_grad[0])
         return dx, dW, db, dgamma, dbeta, None, None, None, None, None
 
 
 class MLPBlockTrain(torch.autograd.Function):
     """The two-conv FeedForwardNet of a GNN layer in training mode (attention_gnn.py:41-44, models/utils.py:48-58) as ONE node:
-    z = (BatchNorm_train(relu(x W0^T + b0))) W3^T + b3.  Same kernels as ConvReluBNTrain followed by Conv1x1, but the BatchNorm output
-    (the widest activation of the layer, 2D channels) was NOT kept for the backward up to round 4 (one fused multiply-add of the saved
-    pre-normalisation activation, recomputed there); it IS kept since round 5: the recomputation was four small launches per row range on
-    the critical path of a step that is bound by launch count, and the 16 MB per layer it saved (0.45 GB per step at 4 x 1024 keypoints)
-    are nothing on a 288 GB part.  OG_TRAIN_KEEP_BN=0 = the old behaviour.  splits: see ConvReluBNTrain."""
+    z = (BatchNorm_train(relu(x W0^T + b0))) W3^T + b3.  Same kernels as ConvReluBNTrain followed by Conv1x1.  The BatchNorm output (the
+    widest activation of the layer, 2D channels) is kept for the backward: recomputing it was four small launches per row range on the
+    critical path of a step that is bound by launch count, and the 16 MB per layer it would save (0.45 GB per step at 4 x 1024 keypoints)
+    are nothing on a 288 GB part.  splits: see ConvReluBNTrain."""
 
     @staticmethod
     def forward(ctx, x, W0, b0, gamma, beta, running_mean, running_var, momentum, eps, splits, W3, b3):
-        a = _gemm_fast(x.detach(), W0.detach().contiguous(), b0.detach(), relu=True)
-        splits = tuple(splits) if splits else (a.shape[0],)
-        if sum(splits) != a.shape[0]:
-            raise ValueError("MLPBlockTrain: splits must add up to the rows of x")
-        y = torch.empty_like(a)
-        stats, r0 = [], 0
-        for rows in splits:
-            _, mean, invstd = batch_norm_train(a[r0:r0 + rows], gamma.detach(), beta.detach(), running_mean, running_var, momentum, eps,
-                                               return_stats=True, out=y[r0:r0 + rows])
-            stats += [mean, invstd]
-            r0 += rows
-        z = _gemm_fast(y, W3.detach().contiguous(), b3.detach())
-        ctx.keep_y = _os.environ.get("OG_TRAIN_KEEP_BN", "1") != "0"
-        ctx.save_for_backward(x, W0, gamma, beta, a, W3, *stats, *((y,) if ctx.keep_y else ()))
-        ctx.splits = splits
+        a = ops.gemm_nt(x.detach(), W0.detach().contiguous(), b0.detach(), relu=True)
+        y, ctx.splits, stats = _bn_forward_ranges(a, gamma, beta, running_mean, running_var, momentum, eps, splits)
+        z = ops.gemm_nt(y, W3.detach().contiguous(), b3.detach())
+        ctx.save_for_backward(x, W0, gamma, a, W3, y, *stats)
         return z
 
     @staticmethod
     def backward(ctx, dzo):
-        lib = _lib.load()
-        x, W0, gamma, beta, a, W3, *stats = ctx.saved_tensors
-        T, C = a.shape
-        dzo = dzo.detach().contiguous()
-        g, bt = gamma.detach(), beta.detach()
-        if ctx.keep_y:
-            y = stats.pop()
-        else:
-            y = torch.empty_like(a)
-            r0 = 0
-            for i, rows in enumerate(ctx.splits):                  # y = (a - mean) invstd gamma + beta, recomputed
-                sc = stats[2 * i + 1] * g
-                torch.addcmul(bt - stats[2 * i] * sc, a[r0:r0 + rows], sc, out=y[r0:r0 + rows])
-                r0 += rows
-        dy, dW3, db3 = _conv_backward(y, W3.detach().contiguous(), dzo, True)
+        x, W0, gamma, a, W3, y, *stats = ctx.saved_tensors
+        dy, dW3, db3 = _conv_backward(y, W3.detach().contiguous(), dzo.detach().contiguous(), True)
         del y
-        dz = torch.empty_like(a)
-        dgamma = dbeta = None
-        r0 = 0
-        for i, rows in enumerate(ctx.splits):
-            mean, invstd = stats[2 * i], stats[2 * i + 1]
-            dg = torch.empty(C, device=a.device, dtype=torch.float32)
-            dbt = torch.empty(C, device=a.device, dtype=torch.float32)
-            a_s, dy_s, dz_s = a[r0:r0 + rows], dy[r0:r0 + rows], dz[r0:r0 + rows]
-            ws = _ws(a, rows, C)
-            with torch.cuda.device(a.device):
-                _lib.check(lib.og_batchnorm_train_backward(a_s.data_ptr(), a_s.stride(0), dy_s.data_ptr(), dy_s.stride(0), rows, C,
-                                                           g.data_ptr(), mean.data_ptr(), invstd.data_ptr(), 1, dz_s.data_ptr(),
-                                                           dz_s.stride(0), dg.data_ptr(), dbt.data_ptr(), ws.data_ptr(), _stream(a)),
-                           "og_batchnorm_train_backward")
-            dgamma = dg if dgamma is None else dgamma + dg
-            dbeta = dbt if dbeta is None else dbeta + dbt
-            r0 += rows
+        dz, dgamma, dbeta = _bn_backward_ranges(a, dy, gamma.detach(), ctx.splits, stats)
         del dy
         dx, dW0, db0 = _conv_backward(x.detach(), W0.detach().contiguous(), dz, ctx.needs_input_grad[0])
         return dx, dW0, db0, dgamma, dbeta, None, None, None, None, None, dW3, db3
@@ -393,15 +307,14 @@ def feed_forward_train_autograd(x: torch.Tensor, net_params, buffers, prefix: st
     (`{prefix}{3i}.weight|bias`, `{prefix}{3i+2}.weight|bias`) to tensors (requires_grad as wanted; conv weights [out, in, 1] or
     [out, in]), `buffers` the BatchNorm running statistics (updated in place).  x: token-major [T, C_in]."""
     n_conv = len({k for k in net_params if k.startswith(prefix) and k.endswith(".weight") and net_params[k].dim() >= 2})
-    if n_conv == 2:                                               # the message MLP of a GNN layer: one node, BatchNorm output not kept
+    if n_conv == 2:                                               # the message MLP of a GNN layer: one node
         W0, W3 = (net_params[f"{prefix}{j}.weight"] for j in (0, 3))
         bn = f"{prefix}2"
-        return MLPBlockTrain.apply(x, W0.reshape(W0.shape[0], W0.shape[1]), net_params[f"{prefix}0.bias"], net_params[bn + ".weight"],
+        return MLPBlockTrain.apply(x, _w2d(W0), net_params[f"{prefix}0.bias"], net_params[bn + ".weight"],
                                    net_params[bn + ".bias"], buffers[bn + ".running_mean"], buffers[bn + ".running_var"], momentum, eps,
-                                   splits, W3.reshape(W3.shape[0], W3.shape[1]), net_params[f"{prefix}3.bias"])
+                                   splits, _w2d(W3), net_params[f"{prefix}3.bias"])
     for i in range(n_conv):
-        W = net_params[f"{prefix}{3 * i}.weight"]
-        W = W.reshape(W.shape[0], W.shape[1])
+        W = _w2d(net_params[f"{prefix}{3 * i}.weight"])
         b = net_params[f"{prefix}{3 * i}.bias"]
         if i + 1 < n_conv:
             bn = f"{prefix}{3 * i + 2}"
@@ -413,21 +326,16 @@ def feed_forward_train_autograd(x: torch.Tensor, net_params, buffers, prefix: st
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# training-mode softmax attention (attention matrix materialised like the reference, attention.py:8-19) and the score matrix
+# training-mode softmax attention (attention.py:8-19) and the score matrix
 def _gemm_raw(dev, A, lda, sA, Bp, ldb, sB, Cp, ldc, sC, M, N, K, batch, scale=1.0):
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.og_gemm_nt(A, lda, sA, Bp, ldb, sB, Cp, ldc, sC, M, N, K, batch, None, 0, None, 0, None, float(scale),
-                                  torch.cuda.current_stream(dev).cuda_stream), "og_gemm_nt")
+    _lib.call("og_gemm_nt", dev, A, lda, sA, Bp, ldb, sB, Cp, ldc, sC, M, N, K, batch, None, 0, None, 0, None, float(scale), _lib.STREAM)
 
 
 def _gemm_km(dev, A, lda, sA, a_kmajor, Bp, ldb, sB, Cp, ldc, sC, M, N, K, batch, k_total=0, scale=1.0, a_colsum=False):
     """og_gemm_kmajor: C[z] = op(A[z]) B[z] with B stored [K][N] and, with a_kmajor, A stored [K][M] (the layouts of the backward products:
     no transposed copies)."""
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        _lib.check(lib.og_gemm_kmajor(A, lda, sA, int(a_kmajor), Bp, ldb, sB, Cp, ldc, sC, M, N, K, batch, int(k_total), int(a_colsum), float(scale),
-                                      torch.cuda.current_stream(dev).cuda_stream), "og_gemm_kmajor")
+    _lib.call("og_gemm_kmajor", dev, A, lda, sA, int(a_kmajor), Bp, ldb, sB, Cp, ldc, sC, M, N, K, batch, int(k_total), int(a_colsum),
+              float(scale), _lib.STREAM)
 
 
 def _r4(n: int) -> int:
@@ -447,9 +355,12 @@ def _heads_last(x: torch.Tensor, B: int) -> torch.Tensor:
     return x.reshape(B, H, N, d).permute(0, 2, 1, 3).reshape(B, N, H * d).contiguous()
 
 
+_FLASH_HEAD_SIZES = (16, 32, 64)
+
+
 def _flash_backward_enabled(dh: int) -> bool:
-    import os
-    return os.environ.get("OG_TRAIN_FLASH_BWD", "1") != "0" and dh in (16, 32, 64)
+    """Read at every call: 0 sends head sizes that have a flash kernel through the GEMM-by-GEMM backward (the tests compare the two)."""
+    return dh in _FLASH_HEAD_SIZES and _env_int("OG_TRAIN_FLASH_BWD", 1, lo=0) != 0
 
 
 _LOG2E = 1.4426950408889634
@@ -461,43 +372,40 @@ def _attention_rows(q2: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor, Bz: in
     binary16 planes in one launch per source matrix (og_split_f16_rows: the q columns scaled by dh^-1/2 and log2(e) on the way -- the same
     two roundings as the tensor multiplications of ops.attention), the output planes come back as fp32 in one (og_merge_f16).
     qkv_of_one: the matrix q2, k2 and v2 are the three column thirds of (then ONE split launch).  -> out [Bz * nq, D], lse [Bz, H, nq]."""
-    lib = _lib.load()
     D = q2.shape[1]
     dh = D // H
     dev = q2.device
-    st = _stream(q2)
     f16 = torch.float16
 
     def split(src, scale_cols):
         rows, cols = src.shape
         hi = torch.empty(rows, cols, device=dev, dtype=f16)
         lo = torch.empty(rows, cols, device=dev, dtype=f16)
-        _lib.check(lib.og_split_f16_rows(src.data_ptr(), src.stride(0), rows, cols, scale_cols, float(dh ** -0.5), _LOG2E, hi.data_ptr(), lo.data_ptr(),
-                                         cols, st), "og_split_f16_rows")
+        _lib.call("og_split_f16_rows", dev, src.data_ptr(), src.stride(0), rows, cols, scale_cols, float(dh ** -0.5), _LOG2E, hi.data_ptr(),
+                  lo.data_ptr(), cols, _lib.STREAM)
         return hi, lo
 
-    with torch.cuda.device(dev):
-        if qkv_of_one is not None:
-            hi, lo = split(qkv_of_one, D)
-            ld = 3 * D
-            planes = [(hi.data_ptr() + 2 * D * i, lo.data_ptr() + 2 * D * i, ld) for i in range(3)]
+    if qkv_of_one is not None:
+        hi, lo = split(qkv_of_one, D)
+        ld = 3 * D
+        planes = [(hi.data_ptr() + 2 * D * i, lo.data_ptr() + 2 * D * i, ld) for i in range(3)]
+    else:
+        qh, ql = split(q2, D)
+        if k2.data_ptr() + 4 * D == v2.data_ptr() and k2.stride(0) == v2.stride(0) == 2 * D:      # k | v: the two halves of one matrix
+            kvh, kvl = split(torch.as_strided(k2, (k2.shape[0], 2 * D), (2 * D, 1)), 0)
+            planes = [(qh.data_ptr(), ql.data_ptr(), D), (kvh.data_ptr(), kvl.data_ptr(), 2 * D), (kvh.data_ptr() + 2 * D, kvl.data_ptr() + 2 * D, 2 * D)]
         else:
-            qh, ql = split(q2, D)
-            if k2.data_ptr() + 4 * D == v2.data_ptr() and k2.stride(0) == v2.stride(0) == 2 * D:      # k | v: the two halves of one matrix
-                kvh, kvl = split(torch.as_strided(k2, (k2.shape[0], 2 * D), (2 * D, 1)), 0)
-                planes = [(qh.data_ptr(), ql.data_ptr(), D), (kvh.data_ptr(), kvl.data_ptr(), 2 * D), (kvh.data_ptr() + 2 * D, kvl.data_ptr() + 2 * D, 2 * D)]
-            else:
-                kh, kl = split(k2, 0)
-                vh, vl = split(v2, 0)
-                planes = [(qh.data_ptr(), ql.data_ptr(), D), (kh.data_ptr(), kl.data_ptr(), D), (vh.data_ptr(), vl.data_ptr(), D)]
-        oh = torch.empty(Bz * nq, D, device=dev, dtype=f16)
-        ol = torch.empty_like(oh)
-        lse = torch.empty(Bz, H, nq, device=dev, dtype=torch.float32)
-        (qh_, ql_, ldq), (kh_, kl_, ldk), (vh_, vl_, ldv) = planes
-        _lib.check(lib.og_attention(qh_, ql_, ldq, kh_, kl_, ldk, vh_, vl_, ldv, oh.data_ptr(), ol.data_ptr(), D, Bz, nq, nk, H, dh, lse.data_ptr(), st),
-                   "og_attention")
-        out = torch.empty(Bz * nq, D, device=dev, dtype=torch.float32)
-        _lib.check(lib.og_merge_f16(oh.data_ptr(), ol.data_ptr(), oh.numel(), out.data_ptr(), st), "og_merge_f16")
+            kh, kl = split(k2, 0)
+            vh, vl = split(v2, 0)
+            planes = [(qh.data_ptr(), ql.data_ptr(), D), (kh.data_ptr(), kl.data_ptr(), D), (vh.data_ptr(), vl.data_ptr(), D)]
+    oh = torch.empty(Bz * nq, D, device=dev, dtype=f16)
+    ol = torch.empty_like(oh)
+    lse = torch.empty(Bz, H, nq, device=dev, dtype=torch.float32)
+    (qh_, ql_, ldq), (kh_, kl_, ldk), (vh_, vl_, ldv) = planes
+    _lib.call("og_attention", dev, qh_, ql_, ldq, kh_, kl_, ldk, vh_, vl_, ldv, oh.data_ptr(), ol.data_ptr(), D, Bz, nq, nk, H, dh, lse.data_ptr(),
+              _lib.STREAM)
+    out = torch.empty(Bz * nq, D, device=dev, dtype=torch.float32)
+    _lib.call("og_merge_f16", dev, oh.data_ptr(), ol.data_ptr(), oh.numel(), out.data_ptr(), _lib.STREAM)
     return out, lse
 
 
@@ -505,21 +413,17 @@ def _flash_backward_rows(q2, k2, v2, out, dout, lse, Bz, nq, nk, H, dq_out, dk_o
     """Flash backward on row-strided operands (og_attention_backward_ld): q2 [Bz * nq, D], k2, v2 [Bz * nk, D] fp32 views with unit column
     stride; dk_out, dv_out: views of the same kind the kernel writes into (column ranges of the [tokens, 3D] gradient matrix of the merged
     projection: no concatenation afterwards); dq_out receives the sum of the per-key-block partials."""
-    lib = _lib.load()
     D = q2.shape[1]
     dh = D // H
     dev = q2.device
-    st = _stream(q2)
     do = dout.detach().to(torch.float32).contiguous()
     delta = torch.empty(Bz * nq * H, device=dev, dtype=torch.float32)
-    parts = lib.og_attention_backward_parts(nk)
+    parts = _lib.load().og_attention_backward_parts(nk)
     dq_part = torch.empty(parts, Bz * nq, D, device=dev, dtype=torch.float32)
-    with torch.cuda.device(dev):
-        _lib.check(lib.og_attention_delta(do.data_ptr(), out.data_ptr(), Bz * nq, H, dh, delta.data_ptr(), st), "og_attention_delta")
-        _lib.check(lib.og_attention_backward_ld(q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), v2.data_ptr(), v2.stride(0), do.data_ptr(),
-                                                lse.data_ptr(), delta.data_ptr(), Bz, nq, nk, H, dh, dh ** -0.5, dq_part.data_ptr(),
-                                                dk_out.data_ptr(), dk_out.stride(0), dv_out.data_ptr(), dv_out.stride(0), st),
-                   "og_attention_backward_ld")
+    _lib.call("og_attention_delta", dev, do.data_ptr(), out.data_ptr(), Bz * nq, H, dh, delta.data_ptr(), _lib.STREAM)
+    _lib.call("og_attention_backward_ld", dev, q2.data_ptr(), q2.stride(0), k2.data_ptr(), k2.stride(0), v2.data_ptr(), v2.stride(0), do.data_ptr(),
+              lse.data_ptr(), delta.data_ptr(), Bz, nq, nk, H, dh, dh ** -0.5, dq_part.data_ptr(),
+              dk_out.data_ptr(), dk_out.stride(0), dv_out.data_ptr(), dv_out.stride(0), _lib.STREAM)
     if parts > 1:
         torch.sum(dq_part, 0, out=dq_out)
     else:
@@ -530,16 +434,13 @@ def _flash_attention_backward(q32, k32, v32, out, dout, H, lse=None):
     """Flash backward (csrc/attention_train.hip): P is recomputed tile by tile in registers from q, k and the row log-sum-exp; nothing
     of size Nq x Nk is ever written.  Token-major contiguous tensors in and out ([B, N, D]): no head-major copies either.  -> dq, dk, dv.
     (The contiguous form of _flash_backward_rows; lse None = no forward kernel left one: an exact-fp32 pass computes it.)"""
-    lib = _lib.load()
     B, Nq, D = q32.shape
     Nk = k32.shape[1]
     dh = D // H
     dev = q32.device
     if lse is None:
         lse = torch.empty(B, H, Nq, device=dev, dtype=torch.float32)
-        with torch.cuda.device(dev):
-            _lib.check(lib.og_attention_train_lse(q32.data_ptr(), k32.data_ptr(), B, Nq, Nk, H, dh, dh ** -0.5, lse.data_ptr(), _stream(q32)),
-                       "og_attention_train_lse")
+        _lib.call("og_attention_train_lse", dev, q32.data_ptr(), k32.data_ptr(), B, Nq, Nk, H, dh, dh ** -0.5, lse.data_ptr(), _lib.STREAM)
     dq, dk, dv = torch.empty_like(q32), torch.empty_like(k32), torch.empty_like(v32)
     _flash_backward_rows(q32.reshape(B * Nq, D), k32.reshape(B * Nk, D), v32.reshape(B * Nk, D), out.reshape(B * Nq, D), dout.reshape(B * Nq, D), lse,
                          B, Nq, Nk, H, dq.reshape(B * Nq, D), dk.reshape(B * Nk, D), dv.reshape(B * Nk, D))
@@ -549,23 +450,22 @@ def _flash_attention_backward(q32, k32, v32, out, dout, H, lse=None):
 class SoftmaxAttention(torch.autograd.Function):
     """out[b, i, h*d:(h+1)*d] = softmax_j(q_h[b, i] . k_h[b, j] / sqrt(d)) v_h[b, j]  on token-major q [B, Nq, D], k, v [B, Nk, D]
     (heads = contiguous channel blocks, attention_gnn.py:24-26).
-    Forward: the flash kernel of the inference path (og_attention: split-f16, never materialises the attention matrix).  Backward:
-    flash too (og_attention_train_lse + og_attention_backward, exact fp32): the attention matrix is recomputed tile by tile in
-    registers -- the reference's autograd keeps B*H*Nq*Nk floats per layer alive (36 layers x 64 MB at 4 x 1024 keypoints); here only
-    q, k, v and the output are saved and nothing of that size is ever written.  OG_TRAIN_FLASH_BWD=0: the attention matrix of the
-    layer is recomputed as a whole (batched GEMM + og_softmax_rows) and the five products run as GEMM launches (other head sizes
-    than 16 / 32 / 64 always do); OG_TRAIN_FLASH=0: round 2's materialising forward."""
+    Head sizes 16 / 32 / 64 -- forward: the flash kernel of the inference path (og_attention: split-f16, never materialises the attention
+    matrix, leaves the row log-sum-exp).  Backward: flash too (og_attention_delta + og_attention_backward_ld, exact fp32): the attention
+    matrix is recomputed tile by tile in registers -- the reference's autograd keeps B*H*Nq*Nk floats per layer alive (36 layers x 64 MB
+    at 4 x 1024 keypoints); here only q, k, v, the output and the log-sum-exp are saved and nothing of that size is ever written.
+    OG_TRAIN_FLASH_BWD=0: the attention matrix of the layer is recomputed as a whole (batched GEMM + og_softmax_rows) and the five
+    products run as GEMM launches.  Other head sizes: the forward materialises the attention matrix the same way (_probs, _pv) and the
+    backward is always the GEMM-by-GEMM one."""
 
     @staticmethod
     def forward(ctx, q, k, v, num_heads):
-        import os
-        from . import ops
         B, Nq, D = q.shape
         d = D // num_heads
         q32, k32, v32 = (t.detach().to(torch.float32).contiguous() for t in (q, k, v))
         ctx.heads = num_heads
         lse = None
-        if os.environ.get("OG_TRAIN_FLASH", "1") != "0" and d in (16, 32, 64):
+        if d in _FLASH_HEAD_SIZES:
             out, lse = ops.attention(q32 * d ** -0.5, k32, v32, num_heads, return_lse=True)
         else:
             P, vh = SoftmaxAttention._probs(q32, k32, v32, num_heads)
@@ -577,7 +477,6 @@ class SoftmaxAttention(torch.autograd.Function):
     @staticmethod
     def _probs(q32, k32, v32, H):
         """P = softmax(scale * Q K^T) [B*H, Nq, r4(Nk)] and the heads-first operands."""
-        lib = _lib.load()
         B, Nq, D = q32.shape
         Nk = k32.shape[1]
         d = D // H
@@ -586,8 +485,7 @@ class SoftmaxAttention(torch.autograd.Function):
         Z, Nk4 = B * H, _r4(Nk)
         P = torch.empty(Z, Nq, Nk4, device=dev, dtype=torch.float32)
         _gemm_raw(dev, qh.data_ptr(), d, Nq * d, kh.data_ptr(), d, Nk * d, P.data_ptr(), Nk4, Nq * Nk4, Nq, Nk, d, Z, d ** -0.5)
-        with torch.cuda.device(dev):
-            _lib.check(lib.og_softmax_rows(P.data_ptr(), Nk4, Z * Nq, Nk, torch.cuda.current_stream(dev).cuda_stream), "og_softmax_rows")
+        _lib.call("og_softmax_rows", dev, P.data_ptr(), Nk4, Z * Nq, Nk, _lib.STREAM)
         return P, (qh, kh, vh)
 
     @staticmethod
@@ -603,7 +501,6 @@ class SoftmaxAttention(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        lib = _lib.load()
         q32, k32, v32, out, *rest = ctx.saved_tensors
         H = ctx.heads
         B, Nq, D = q32.shape
@@ -615,7 +512,6 @@ class SoftmaxAttention(torch.autograd.Function):
         Z, Nq, d = qh.shape
         Nk = kh.shape[1]
         dev = qh.device
-        st = torch.cuda.current_stream(dev).cuda_stream
         Nk4 = _r4(Nk)
         doh = _heads_first(dout.detach().to(torch.float32), H)                                  # [Z, Nq, d]
         # every product below reads its operands as they lie (og_gemm_kmajor): no transposed copy of P, dS, dO, Q or K
@@ -625,8 +521,7 @@ class SoftmaxAttention(torch.autograd.Function):
         # dP = dO V^T  ->  dS = scale * P o (dP - rowsum(dP o P))
         dS = torch.empty(Z, Nq, Nk4, device=dev, dtype=torch.float32)
         _gemm_raw(dev, doh.data_ptr(), d, Nq * d, vh.data_ptr(), d, Nk * d, dS.data_ptr(), Nk4, Nq * Nk4, Nq, Nk, d, Z)
-        with torch.cuda.device(dev):
-            _lib.check(lib.og_softmax_rows_backward(P.data_ptr(), dS.data_ptr(), Nk4, Z * Nq, Nk, d ** -0.5, st), "og_softmax_rows_backward")
+        _lib.call("og_softmax_rows_backward", dev, P.data_ptr(), dS.data_ptr(), Nk4, Z * Nq, Nk, d ** -0.5, _lib.STREAM)
         del P
         # dQ = dS K   (columns [Nk, Nk4) of dS are zero; K gets zero rows up to Nk4)
         kp = _pad_rows(kh, Nk4)
@@ -667,13 +562,13 @@ class ProjectedAttention(torch.autograd.Function):
         D = Wq.shape[0]
         if xkv is None:
             Wc, bc = stack if stack is not None else (torch.cat([Wq, Wk, Wv]), torch.cat([bq, bk, bv]))
-            qkv = _gemm_fast(xq, Wc, bc)                                                         # [T, 3D]
+            qkv = ops.gemm_nt(xq, Wc, bc)                                                        # [T, 3D]
             out, lse = _attention_rows(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], Bz, nq, nk, H, qkv_of_one=qkv)
             saved = (xq, Wc, bc, out, lse)
         else:
             Wq_, bq, Wkv, bkv = stack if stack is not None else (Wq.contiguous(), bq, torch.cat([Wk, Wv]), torch.cat([bk, bv]))
-            q = _gemm_fast(xq, Wq_, bq)
-            kv = _gemm_fast(xkv, Wkv, bkv)                                                       # [Tk, 2D]
+            q = ops.gemm_nt(xq, Wq_, bq)
+            kv = ops.gemm_nt(xkv, Wkv, bkv)                                                      # [Tk, 2D]
             out, lse = _attention_rows(q, kv[:, :D], kv[:, D:], Bz, nq, nk, H)
             saved = (xq, Wq_, bq, out, lse, xkv, Wkv, bkv)
         ctx.geom = (Bz, nq, nk, H, xkv is None)
@@ -686,7 +581,7 @@ class ProjectedAttention(torch.autograd.Function):
         if is_self:
             xq, Wc, bc, out, lse = ctx.saved_tensors
             D = Wc.shape[0] // 3
-            qkv = _gemm_fast(xq, Wc, bc)
+            qkv = ops.gemm_nt(xq, Wc, bc)
             dqkv = torch.empty_like(qkv)
             _flash_backward_rows(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], out, dout.reshape(Bz * nq, D), lse, Bz, nq, nk, H,
                                  dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:])
@@ -695,8 +590,8 @@ class ProjectedAttention(torch.autograd.Function):
             return (dx, None, dW[:D], db[:D], dW[D:2 * D], db[D:2 * D], dW[2 * D:], db[2 * D:], None, None, None, None, None)
         xq, Wq, bq, out, lse, xkv, Wkv, bkv = ctx.saved_tensors
         D = Wq.shape[0]
-        q = _gemm_fast(xq, Wq, bq)
-        kv = _gemm_fast(xkv, Wkv, bkv)
+        q = ops.gemm_nt(xq, Wq, bq)
+        kv = ops.gemm_nt(xkv, Wkv, bkv)
         dq = torch.empty_like(q)
         dkv = torch.empty_like(kv)
         _flash_backward_rows(q, kv[:, :D], kv[:, D:], out, dout.reshape(Bz * nq, D), lse, Bz, nq, nk, H, dq, dkv[:, :D], dkv[:, D:])
@@ -847,8 +742,7 @@ def _seq_state(seq: torch.nn.Module):
 
 def _mlp_train(x2d: torch.Tensor, seq: torch.nn.Module, momentum: float = 0.1, eps: float = 1e-5, splits=None) -> torch.Tensor:
     params, buffers = _seq_state(seq)
-    W0 = params["0.weight"]
-    x2d, W0p = _pad_k4(x2d, W0.reshape(W0.shape[0], W0.shape[1]))
+    x2d, W0p = _pad_k4(x2d, _w2d(params["0.weight"]))
     params = dict(params)
     params["0.weight"] = W0p
     y = feed_forward_train_autograd(x2d.contiguous(), params, buffers, "", momentum, eps, splits)
@@ -866,8 +760,7 @@ def _mlp_frozen(x2d: torch.Tensor, seq: torch.nn.Module, siren: bool = False, ep
     idx = sorted({int(k.split(".")[0]) for k in params if k.endswith(".weight") and params[k].dim() == 3})
     y = x2d
     for n_, i in enumerate(idx):
-        W = params[f"{i}.weight"]
-        W2 = W.reshape(W.shape[0], W.shape[1])
+        W2 = _w2d(params[f"{i}.weight"])
         if n_ == 0:
             y, W2 = _pad_k4(y, W2)
         y = Conv1x1.apply(y.contiguous(), W2, params[f"{i}.bias"])
@@ -926,12 +819,12 @@ def superglue_forward_train(model, data, frozen_bn: bool = False):
     x0, x1 = xs[:T0], xs[T0:]
 
     def conv(x2d, c):
-        return Conv1x1.apply(x2d.contiguous(), c.weight.reshape(c.weight.shape[0], c.weight.shape[1]), c.bias)
+        return Conv1x1.apply(x2d.contiguous(), _w2d(c.weight), c.bias)
 
     def conv_many(x2d, *cs):
         """Several 1x1 convs of the SAME input as one GEMM (weights stacked along the output channels; autograd splits the gradient):
         at 4096 tokens a [T, 256] x [256, 256] launch is 64 workgroups on 256 CUs -- merged launches fill the chip."""
-        W = torch.cat([c.weight.reshape(c.weight.shape[0], c.weight.shape[1]) for c in cs])
+        W = torch.cat([_w2d(c.weight) for c in cs])
         b = torch.cat([c.bias for c in cs])
         return Conv1x1.apply(x2d.contiguous(), W, b).split([c.weight.shape[0] for c in cs], dim=1)
 
@@ -946,21 +839,15 @@ def superglue_forward_train(model, data, frozen_bn: bool = False):
         y = torch.cat([xq - msg if model.use_offset else xq, msg], dim=-1)
         return xq + mlp(y, layer.module.fc, splits)
 
-    import os
-    fused_attn = (not model.linear_attention and not model.favor_relu and _flash_backward_enabled(D // H)
-                  and os.environ.get("OG_TRAIN_FLASH", "1") != "0")
-
-    def w2(c):
-        return c.weight.reshape(c.weight.shape[0], c.weight.shape[1])
-
+    fused_attn = not model.linear_attention and not model.favor_relu and _flash_backward_enabled(D // H)
     stacks = {}                                                                    # per forward call: (layer, form) -> stacked projection weights
 
     def proj_attend(mha, xq, xkv, Bz, nq, nk):                                     # projections + attention, q / k / v not kept
         key = (id(mha), xkv is None)
         if key not in stacks:
             stacks[key] = ProjectedAttention.stacked(mha, xkv is None)
-        return ProjectedAttention.apply(xq, xkv, w2(mha.in_proj_q), mha.in_proj_q.bias, w2(mha.in_proj_k), mha.in_proj_k.bias,
-                                        w2(mha.in_proj_v), mha.in_proj_v.bias, Bz, nq, nk, H, stacks[key])
+        return ProjectedAttention.apply(xq, xkv, _w2d(mha.in_proj_q.weight), mha.in_proj_q.bias, _w2d(mha.in_proj_k.weight), mha.in_proj_k.bias,
+                                        _w2d(mha.in_proj_v.weight), mha.in_proj_v.bias, Bz, nq, nk, H, stacks[key])
 
     for li, layer in enumerate(model.attention_gnn.layers):
         mha = layer.module.mha

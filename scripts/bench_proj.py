@@ -36,7 +36,7 @@ for D, M in ((256, 65536), (128, 65536), (128, 131072)):
     forms = {"self": (M, 0, (0, 0), (0, N)), "cross": (M, M // 2, (0, D), (0, N)), "kv": (M // 2, 0, (0, 0), (D, N))}
     for name, (R, split, ca, cb) in forms.items():
         def blk():
-            rc = lib.og_proj_block(rows.data_ptr(), 2 * D, R, D, sd.data_ptr(), b.data_ptr(), inv.data_ptr(), yh.data_ptr(), yl.data_ptr(), N,
+            rc = lib.og_proj_block(rows.data_ptr(), 2 * D, R, D, N, sd.data_ptr(), b.data_ptr(), inv.data_ptr(), yh.data_ptr(), yl.data_ptr(), N,
                                    split, ca[0] // 32, ca[1] // 32, cb[0] // 32, cb[1] // 32, st)
             assert rc == 0, rc
         us = timed(blk)

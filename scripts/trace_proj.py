@@ -20,7 +20,7 @@ for D, M in ((256, 65536), (256, 32768), (128, 65536)):
     inv = torch.full((1,), 1.0 / 256.0, device=dev)
     yh = torch.zeros(M, N, device=dev, dtype=torch.float16); yl = torch.zeros_like(yh)
     def run():
-        assert lib.og_proj_block(rows.data_ptr(), 2 * D, M, D, sd.data_ptr(), b.data_ptr(), inv.data_ptr(), yh.data_ptr(), yl.data_ptr(), N, 0, 0, 0, 0, N // 32, st) == 0
+        assert lib.og_proj_block(rows.data_ptr(), 2 * D, M, D, N, sd.data_ptr(), b.data_ptr(), inv.data_ptr(), yh.data_ptr(), yl.data_ptr(), N, 0, 0, 0, 0, N // 32, st) == 0
     for _ in range(3): run()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize(); e0.record()

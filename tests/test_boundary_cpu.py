@@ -466,3 +466,34 @@ def test_training_stacked_projection_weights_follow_their_parameters():
     Wq, bq, Wkv, bkv = PA.stacked(m, False)
     assert Wkv.shape == (16, 8) and torch.equal(Wkv[:8], w(m.in_proj_k)) and torch.equal(bkv[8:], m.in_proj_v.bias) and torch.equal(Wq, w(m.in_proj_q))
     assert len(m.state_dict()) == 6 and not any(t.requires_grad for t in PA.stacked(m, True))
+
+
+def _package_sources():
+    pkg = os.path.join(ROOT, "openglue_amd")
+    return {f: open(os.path.join(pkg, f)).read() for f in sorted(os.listdir(pkg)) if f.endswith(".py")}
+
+
+def test_library_calls_are_made_in_one_place():
+    """How a launch is made (device guard, the current stream of the tensors' device, the return code checked under the symbol's own
+    name) and the helpers around it live in _lib.py alone: no other module reads a raw stream handle or keeps its own copy of them.
+    (SuperPoint._workspace is a method that sizes a buffer, not a copy of the aligned-workspace helper.)"""
+    src = _package_sources()
+    assert ".cuda_stream" in src["_lib.py"]
+    assert [f for f, text in src.items() if f != "_lib.py" and ".cuda_stream" in text] == []
+    copies = []
+    for f, text in src.items():
+        for m in re.finditer(r"^( *)def (_stream|_ptr|_gpu|_req|_workspace)\b", text, flags=re.M):
+            if f != "_lib.py" and not (f == "superpoint.py" and m.group(2) == "_workspace" and m.group(1)):
+                copies.append((f, m.group(2)))
+    assert copies == []
+    launched = [(f, name) for f, text in src.items() for name in re.findall(r"""_lib\.call\(\s*["'](\w+)["']""", text)]
+    assert len(launched) > 40, len(launched)
+    assert [(f, name) for f, name in launched if name not in _lib.SYMBOLS] == []
+
+
+def test_closed_training_experiments_are_gone():
+    """The split-f16 training convs, the recomputed BatchNorm output and the user-set forward switch were measured and closed
+    (profiles/): neither the knobs nor a mention of them is left in the package.  OG_TRAIN_FLASH_BWD stays."""
+    for f, text in _package_sources().items():
+        for pattern in (r"OG_TRAIN_F16X3", r"OG_TRAIN_KEEP_BN", r"OG_TRAIN_FLASH(?!_BWD)"):
+            assert not re.search(pattern, text), (f, pattern)
