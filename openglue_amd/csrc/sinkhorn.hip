@@ -884,7 +884,10 @@ int og_launch_sinkhorn_trajectory(const float* S, int64_t lds, const float* dust
     const double norm = -log((double)m + (double)n);
     const float la = (float)norm, lb = (float)norm;
     const float la_bin = (float)norm + (float)log((double)n), lb_bin = (float)norm + (float)log((double)m);
-    hipError_t e = hipMemsetAsync(V, 0, sizeof(float) * (size_t)B * w.ldv, st);          // v_0 = 0 (optimal_transport.py:22)
+    // v_0 = 0 (optimal_transport.py:22) -- and the whole trajectory with it: the sweep loads v_in in groups of four columns, so for n % 4 == 1 or 2
+    // it touches the gap columns (n, ldv) of v_t, which the combine never writes.  They meet -inf and contribute exp(-inf) = 0 unless they hold NaN or
+    // +inf, as a recycled workspace can: then every score of the call was NaN.
+    hipError_t e = hipMemsetAsync(V, 0, sizeof(float) * (size_t)(iters + 1) * B * w.ldv, st);
     if (e != hipSuccess) return (int)e;
     const SinkhornGeom g = sk_geom(n);
     const RaggedNone rd{};

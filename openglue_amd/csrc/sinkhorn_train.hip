@@ -14,7 +14,7 @@
 //                                            dZ_ij -= du_t,i Wu_ij ;  dv_t-1,j -= sum_i du_t,i Wu_ij
 // for t = T .. 1 (u_t only feeds v_t and, for t = T, the output; v_0 = 0 is a constant).  The two steps of an iteration are
 // ONE sweep: a row is owned by one wave, so du_t,i is complete after the row's first pass and the u-step of the same row
-// follows at once; dv_t-1 is accumulated per wave in registers and added atomically per column (fp32 atomics: the summation
+// follows at once; dv_t-1 is accumulated per wave (registers; LDS in the wide instances) and added atomically per column (fp32 atomics: the summation
 // order, hence the last bits of the gradients, can differ from run to run).  The augmented (m+1) x (n+1) matrix is
 // materialised here (training keeps activations anyway); dS = dZ[:m,:n] / reg, d dustbin = sum of dZ over the dustbin row
 // and column / reg.  Training-path code: written for clarity, not tuned.
@@ -93,52 +93,97 @@ __global__ __launch_bounds__(256) void sk_bwd_iter_kernel(const float* __restric
     const float* vt = v_t + (int64_t)b * ldv;
     const float* vp = v_prev + (int64_t)b * ldv;
     const float* dvt = dv_t + (int64_t)b * ldv;
-    float colacc[CH];                                            // the per-column vectors are re-read per row (L1/L2 hits): registers
-#pragma unroll                                                  // hold one row of Z, one of weights and the column accumulators
-    for (int c = 0; c < CH; ++c) colacc[c] = 0.f;
-    for (int row = blockIdx.x * 4 + wave; row <= M; row += 4 * gridDim.x) {
-        const float* za = Za + ((int64_t)b * (M + 1) + row) * lda;
-        float* dz = dZ + ((int64_t)b * (M + 1) + row) * lda;
-        const float ui = ub[row];
-        const float lai = row < M ? la : la_bin;
-        float zr[CH], wv[CH];
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const int j = lane + 64 * c;
-            zr[c] = j <= N ? za[j] : OG_NEG_INF;
-            const float vtl = j <= N ? vt[j] - (j < N ? lb : lb_bin) : 0.f;             // v_t,j - lb_j
-            const float dvl = j <= N ? dvt[j] : 0.f;
-            wv[c] = dvl * __expf(zr[c] + ui + vtl);              // dv_t,j * Wv_ij   (exp(-inf) = 0 beyond the matrix)
-            acc += wv[c];
-        }
-        acc = wave_sum(acc);
-        const float dui = (du_is_fresh ? du[(int64_t)b * ldu + row] : 0.f) - acc;      // complete du_t,i
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            const int j = lane + 64 * c;
-            if (j <= N) {
-                const float wu = dui * __expf(zr[c] + vp[j] + ui - lai);                // du_t,i * Wu_ij
-                dz[j] -= wv[c] + wu;
-                colacc[c] -= wu;
+    if constexpr (CH > 17) {
+        // Wide instances (n >= 1088).  Three arrays of CH floats per lane (the row of Z, its weights, the column accumulators) do not fit the
+        // register file: as the narrow form below, <65> spilled 274 VGPRs to 1048 bytes of scratch per lane and <33> sat at 256 + 82
+        // registers.  Here nothing per column lives in a register: the accumulators are a private LDS slice per wave (lane l owns words
+        // c * 64 + l: no bank conflict, no barrier until the end), the second pass reads the row of Z and the column vectors again (the
+        // first pass has just pulled them into L1 / L2) and recomputes Wv, and the chunk loops stop at the chunks the matrix has.  Same
+        // summation order per lane, wave and workgroup as the narrow form.
+        __shared__ float cacc[4][CH * 64];
+        float* mine = cacc[wave];
+        const int nch = (N + 1 + 63) >> 6;                        // <= CH (the host picks CH from this)
+        for (int c = 0; c < nch; ++c) mine[c * 64 + lane] = 0.f;
+        for (int row = blockIdx.x * 4 + wave; row <= M; row += 4 * gridDim.x) {
+            const float* za = Za + ((int64_t)b * (M + 1) + row) * lda;
+            float* dz = dZ + ((int64_t)b * (M + 1) + row) * lda;
+            const float ui = ub[row];
+            const float lai = row < M ? la : la_bin;
+            float acc = 0.f;
+#pragma unroll 4
+            for (int c = 0; c < nch; ++c) {
+                const int j = lane + 64 * c;
+                if (j <= N) acc += dvt[j] * __expf(za[j] + ui + (vt[j] - (j < N ? lb : lb_bin)));      // dv_t,j * Wv_ij
+            }
+            acc = wave_sum(acc);
+            const float dui = (du_is_fresh ? du[(int64_t)b * ldu + row] : 0.f) - acc;      // complete du_t,i
+#pragma unroll 4
+            for (int c = 0; c < nch; ++c) {
+                const int j = lane + 64 * c;
+                if (j <= N) {
+                    const float zc = za[j];
+                    const float wvc = dvt[j] * __expf(zc + ui + (vt[j] - (j < N ? lb : lb_bin)));
+                    const float wu = dui * __expf(zc + vp[j] + ui - lai);                   // du_t,i * Wu_ij
+                    dz[j] -= wvc + wu;
+                    mine[c * 64 + lane] -= wu;
+                }
             }
         }
-    }
-    // the four waves of the workgroup meet in LDS first (wave order), then ONE atomic per column and workgroup: the row grid grew from 64 to 128
-    // workgroups per pair (a wave walks two rows instead of four to five) with half the atomics per workgroup-row it had: backward of
-    // 4 x 1024 x 1024 x 20 iterations 1.23 -> 0.93 ms
-    __shared__ float red[3][CH * 64];
-    if (wave) {
+        __syncthreads();
+        if (wave) return;
+        for (int c = 0; c < nch; ++c) {
+            const int j = lane + 64 * c, o = c * 64 + lane;
+            const float sum = ((cacc[0][o] + cacc[1][o]) + cacc[2][o]) + cacc[3][o];
+            if (j <= N && sum != 0.f) atomicAdd(dv_prev + (int64_t)b * ldv + j, sum);
+        }
+    } else {
+        float colacc[CH];                                            // the per-column vectors are re-read per row (L1/L2 hits): registers
+#pragma unroll                                                  // hold one row of Z, one of weights and the column accumulators
+        for (int c = 0; c < CH; ++c) colacc[c] = 0.f;
+        for (int row = blockIdx.x * 4 + wave; row <= M; row += 4 * gridDim.x) {
+            const float* za = Za + ((int64_t)b * (M + 1) + row) * lda;
+            float* dz = dZ + ((int64_t)b * (M + 1) + row) * lda;
+            const float ui = ub[row];
+            const float lai = row < M ? la : la_bin;
+            float zr[CH], wv[CH];
+            float acc = 0.f;
 #pragma unroll
-        for (int c = 0; c < CH; ++c) red[wave - 1][c * 64 + lane] = colacc[c];
-    }
-    __syncthreads();
-    if (wave) return;
+            for (int c = 0; c < CH; ++c) {
+                const int j = lane + 64 * c;
+                zr[c] = j <= N ? za[j] : OG_NEG_INF;
+                const float vtl = j <= N ? vt[j] - (j < N ? lb : lb_bin) : 0.f;             // v_t,j - lb_j
+                const float dvl = j <= N ? dvt[j] : 0.f;
+                wv[c] = dvl * __expf(zr[c] + ui + vtl);              // dv_t,j * Wv_ij   (exp(-inf) = 0 beyond the matrix)
+                acc += wv[c];
+            }
+            acc = wave_sum(acc);
+            const float dui = (du_is_fresh ? du[(int64_t)b * ldu + row] : 0.f) - acc;      // complete du_t,i
 #pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const int j = lane + 64 * c;
-        const float sum = ((colacc[c] + red[0][c * 64 + lane]) + red[1][c * 64 + lane]) + red[2][c * 64 + lane];
-        if (j <= N && sum != 0.f) atomicAdd(dv_prev + (int64_t)b * ldv + j, sum);
+            for (int c = 0; c < CH; ++c) {
+                const int j = lane + 64 * c;
+                if (j <= N) {
+                    const float wu = dui * __expf(zr[c] + vp[j] + ui - lai);                // du_t,i * Wu_ij
+                    dz[j] -= wv[c] + wu;
+                    colacc[c] -= wu;
+                }
+            }
+        }
+        // the four waves of the workgroup meet in LDS first (wave order), then ONE atomic per column and workgroup: the row grid grew from 64 to 128
+        // workgroups per pair (a wave walks two rows instead of four to five) with half the atomics per workgroup-row it had: backward of
+        // 4 x 1024 x 1024 x 20 iterations 1.23 -> 0.93 ms
+        __shared__ float red[3][CH * 64];
+        if (wave) {
+#pragma unroll
+            for (int c = 0; c < CH; ++c) red[wave - 1][c * 64 + lane] = colacc[c];
+        }
+        __syncthreads();
+        if (wave) return;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            const int j = lane + 64 * c;
+            const float sum = ((colacc[c] + red[0][c * 64 + lane]) + red[1][c * 64 + lane]) + red[2][c * 64 + lane];
+            if (j <= N && sum != 0.f) atomicAdd(dv_prev + (int64_t)b * ldv + j, sum);
+        }
     }
 }
 

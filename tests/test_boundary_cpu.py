@@ -151,6 +151,21 @@ def test_error_behaviour():
     assert lib.og_check_shape(C.byref(s)) == -2
     s = model._shape(1, 16, 16); s.flags = 64
     assert lib.og_check_shape(C.byref(s)) == -4
+    # linear attention has no head-size-128 kernel: og_check_shape says so, instead of og_forward failing after the encoder was enqueued
+    wide = syn.make_config(descriptor_dim=256, num_stages=1, num_heads=2, num_iters=3)
+    assert lib.og_check_shape(C.byref(SuperGlue(wide).eval()._shape(1, 16, 16))) == 0
+    lin = dict(wide); lin["attention_gnn"] = dict(wide["attention_gnn"], attention="linear")
+    s = SuperGlue(lin).eval()._shape(1, 16, 16)
+    assert s.flags & _lib.OG_FLAG_LINEAR_ATTENTION and lib.og_check_shape(C.byref(s)) == -2 and lib.og_workspace_bytes(C.byref(s)) == 0
+    s.num_heads = 4                                             # head size 64: supported
+    assert lib.og_check_shape(C.byref(s)) == 0
+    # the training Sinkhorn: n <= 4159 (the backward's widest instance) and iters >= 1, refused before any launch
+    fake = 0x10000
+    assert lib.og_sinkhorn_train_workspace_bytes(1, 8, 4159, 3) > 0
+    assert lib.og_sinkhorn_train_workspace_bytes(1, 8, 4160, 3) == 0 and lib.og_sinkhorn_train_workspace_bytes(1, 8, 4159, 0) == 0
+    for n_, it_ in ((4160, 3), (4159, 0)):
+        assert lib.og_sinkhorn_train_forward(fake, 4160, 1.0, None, 1, 8, n_, it_, 1.0, fake, fake, None) == -1
+        assert lib.og_sinkhorn_backward(fake, 4160, 1.0, None, 1, 8, n_, it_, 1.0, fake, fake, fake, 4160, None, None) == -1
     # NULL arguments are rejected before any launch (no GPU needed)
     assert lib.og_forward(None, None, None, None, None, None) == -1
     assert lib.og_gemm_nt(None, 4, 0, None, 4, 0, None, 4, 0, 1, 1, 4, 1, None, 0, None, 0, None, 1.0, None) == -1

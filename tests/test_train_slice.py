@@ -518,6 +518,45 @@ def test_softmax_attention_backward_against_float64(gpu_device, shape, flash_bwd
         assert err < 2e-5, (name, float(err))
 
 
+# ----------------------------------------------------------------------------- the O(N) attentions in isolation (LinearAttentionCore)
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,shape", [("linear", (2, 37, 53, 4, 16)), ("linear", (1, 130, 97, 2, 32)), ("linear", (2, 200, 333, 4, 64)),
+                                        ("linear", (1, 1, 4099, 2, 64)), ("linear", (1, 2048, 2047, 4, 64)), ("linear", (1, 1000, 1, 2, 128)),
+                                        ("favor", (2, 130, 97, 1, 256)), ("favor", (1, 1025, 2049, 1, 128)), ("favor", (2, 5, 3, 1, 64))])
+def test_linear_attention_core_against_float64(gpu_device, kind, shape):
+    """train.linear_attention_elu_train / train.favor_relu_attention_train (LinearAttentionCore: five batched og_gemm_kmajor / og_gemm_nt
+    contractions forward, six backward) vs torch autograd in float64 of the oracle's formulation, dense random cotangent: every head size
+    (128 included: training does not go through linear_attention_kernel), key counts that are not multiples of 4 at size, one query,
+    one key.  Output, dq, dk, dv each within 2e-5 of the reference relative to that tensor's own float64 maximum (the bar of the softmax
+    test above; the float32 CPU formulation is within 1e-6).  With a single key the output is v whatever q and k are: dq and dk are zero
+    in exact arithmetic and rounding noise in float32, so that row bounds them absolutely."""
+    from openglue_amd import train
+    B, Nq, Nk, H, d = shape
+    D = H * d
+    g = torch.Generator().manual_seed(Nq * 3 + Nk + d)
+    q, k, v = (torch.randn(B, n_, D, generator=g) for n_ in (Nq, Nk, Nk))
+    R = torch.randn(B, Nq, D, generator=g)
+    P = torch.randn(2 * D, D, generator=g) if kind == "favor" else None
+    qd, kd, vd = (t.double().requires_grad_(True) for t in (q, k, v))
+    ref = orc.linear_attention_elu(qd, kd, vd, H) if kind == "linear" else orc.favor_relu_attention(qd, kd, vd, P.double())
+    (ref * R.double()).sum().backward()
+    qg, kg, vg = (t.to(gpu_device).requires_grad_(True) for t in (q, k, v))
+    out = train.linear_attention_elu_train(qg, kg, vg, H) if kind == "linear" else train.favor_relu_attention_train(qg, kg, vg, P.to(gpu_device))
+    (out * R.to(gpu_device)).sum().backward()
+    err = ((out.detach().cpu().double() - ref.detach()).abs().max() / ref.detach().abs().max()).item()
+    print(f"[{kind} core {shape}] out rel err {err:.2e} (tol 2e-05)")
+    assert err < 2e-5, err
+    for name, got, want in (("dq", qg.grad, qd.grad), ("dk", kg.grad, kd.grad), ("dv", vg.grad, vd.grad)):
+        if Nk == 1 and name != "dv":
+            bound = 1e-5 * R.abs().max().item() * v.abs().max().item()
+            print(f"[{kind} core {shape}] {name} max {got.abs().max().item():.2e} (one key: exact value 0, bound {bound:.2e})")
+            assert got.abs().max().item() <= bound and want.abs().max().item() <= bound, (name, got.abs().max().item())
+            continue
+        err = ((got.cpu().double() - want).abs().max() / want.abs().max()).item()
+        print(f"[{kind} core {shape}] {name} rel err {err:.2e} (tol 2e-05)")
+        assert err < 2e-5, (name, err)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", [(2, 37, 53, 4, 16), (1, 130, 97, 2, 32), (2, 200, 333, 4, 64)])
 def test_row_log_sum_exp_from_both_kernels(gpu_device, shape):
@@ -607,6 +646,85 @@ def test_training_glue_kernels(gpu_device):
     delta = torch.empty(77 * 4, device=gpu_device)
     _lib.check(lib.og_attention_delta(a.data_ptr(), b.data_ptr(), 77, 4, 16, delta.data_ptr(), st), "delta")
     assert (delta.reshape(77, 4).double() - (a.double() * b.double()).reshape(77, 4, 16).sum(-1)).abs().max() < 1e-5
+
+
+@pytest.mark.gpu
+def test_training_helper_entries_against_float64(gpu_device):
+    """og_softmax_rows / og_softmax_rows_backward, og_transpose_f32(_batched), og_colsum_f32 on their own (the training step reaches them only
+    through the GEMM-by-GEMM attention backward, at the few shapes those cases have) against plain tensor algebra in float64."""
+    from openglue_amd import _lib
+    dev = gpu_device
+    g = torch.Generator().manual_seed(23)
+    nan = float("nan")
+    # ---- row softmax, forward and backward, in place, padded rows whose gap is dirty
+    cases = [(r, c, "randn") for r, c in ((1, 1), (5, 63), (130, 64), (77, 65), (1000, 1027))] + [(9, 300, "span"), (6, 130, "equal")]
+    for rows, cols, fill in cases:
+        ld = (cols + 3) // 4 * 4 + 4
+        x = torch.randn(rows, cols, generator=g) * 3
+        if fill == "span":                                      # logits from -1e4 to 1e4 in every row: only the max-subtracted form survives
+            x = torch.linspace(-1e4, 1e4, cols)[None, :].repeat(rows, 1) + torch.randn(rows, cols, generator=g)
+        if fill == "equal":
+            x[2, :] = 7.5                                       # a row of equal values: 1 / cols everywhere
+        buf = torch.full((rows, ld), nan); buf[:, :cols] = x
+        Pg = buf.to(dev)
+        _lib.call("og_softmax_rows", dev, Pg.data_ptr(), ld, rows, cols, _lib.STREAM)
+        P = Pg.cpu()
+        want = torch.softmax(x.double(), -1)
+        eP, eS = (P[:, :cols].double() - want).abs().max().item(), (P[:, :cols].double().sum(-1) - 1).abs().max().item()
+        print(f"[softmax_rows {rows}x{cols} ld {ld} {fill}] P err {eP:.2e}, row-sum err {eS:.2e} (tol 2e-06)")
+        assert eP <= 2e-6 and eS <= 2e-6
+        assert torch.all(P[:, cols:] == 0)                     # the gap is zeroed (it held NaN)
+        if fill == "equal":
+            assert (P[2, :cols].double() - 1.0 / cols).abs().max().item() <= 2e-6
+        dP = torch.randn(rows, cols, generator=g)
+        dbuf = torch.full((rows, ld), nan); dbuf[:, :cols] = dP
+        Pn = P.clone(); Pn[:, cols:] = nan                      # P's own gap is not read either
+        dg, Pn = dbuf.to(dev), Pn.to(dev)
+        _lib.call("og_softmax_rows_backward", dev, Pn.data_ptr(), dg.data_ptr(), ld, rows, cols, 0.37, _lib.STREAM)
+        dS = dg.cpu()
+        P64 = P[:, :cols].double()
+        wantS = 0.37 * P64 * (dP.double() - (dP.double() * P64).sum(-1, keepdim=True))
+        tol = 2e-6 * max(wantS.abs().max().item(), 1e-30) * max(1.0, cols ** 0.5 / 8)
+        eD = (dS[:, :cols].double() - wantS).abs().max().item()
+        print(f"[softmax_rows_backward {rows}x{cols} ld {ld} {fill}] dS err {eD:.2e} tol {tol:.2e}")
+        assert eD <= tol
+        assert torch.all(dS[:, cols:] == 0)
+    # ---- transposes: bit-equal, nothing outside the destination matrix written
+    for rows, cols in ((1, 1), (63, 65), (64, 64), (1000, 36), (129, 300)):
+        lds_, ldd = cols + 3, rows + 5
+        src = torch.randn(rows, lds_, generator=g)
+        dst = torch.full((cols, ldd), -7.25, device=dev)
+        sg = src.to(dev)
+        _lib.call("og_transpose_f32", dev, sg.data_ptr(), lds_, rows, cols, dst.data_ptr(), ldd, _lib.STREAM)
+        got = dst.cpu()
+        assert torch.equal(got[:, :rows], src[:, :cols].T) and torch.all(got[:, rows:] == -7.25), (rows, cols)
+        Z, ss, sd_ = 3, rows * lds_ + 8, cols * ldd + 12
+        srcb = torch.randn(Z * ss, generator=g)
+        dstb = torch.full((Z * sd_,), -7.25, device=dev)
+        sgb = srcb.to(dev)
+        _lib.call("og_transpose_f32_batched", dev, sgb.data_ptr(), lds_, ss, rows, cols, dstb.data_ptr(), ldd, sd_, Z, _lib.STREAM)
+        gotb = dstb.cpu()
+        for z in range(Z):
+            s_z = srcb[z * ss:z * ss + rows * lds_].view(rows, lds_)
+            d_z = gotb[z * sd_:z * sd_ + cols * ldd].view(cols, ldd)
+            assert torch.equal(d_z[:, :rows], s_z[:, :cols].T) and torch.all(d_z[:, rows:] == -7.25), (rows, cols, z)
+            assert torch.all(gotb[z * sd_ + cols * ldd:(z + 1) * sd_] == -7.25)
+    # ---- column sums
+    lib = _lib.load()
+    for rows, ch in ((1, 4), (77, 36), (8192, 256), (65536, 64)):
+        ldx = ch + 4
+        x = torch.randn(rows, ldx, generator=g)
+        xg = x.to(dev)
+        out = torch.full((ch + 2,), -7.25, device=dev)
+        ws, wp = _lib.workspace(lib.og_batchnorm_train_workspace_bytes(rows, (ch + 3) // 4 * 4), dev)
+        _lib.call("og_colsum_f32", dev, xg.data_ptr(), ldx, rows, ch, out.data_ptr(), wp, _lib.STREAM)
+        got = out.cpu()
+        want = x[:, :ch].double().sum(0)
+        tol = 2e-6 * max(want.abs().max().item(), rows ** 0.5)
+        e = (got[:ch].double() - want).abs().max().item()
+        print(f"[colsum {rows}x{ch}] err {e:.2e} tol {tol:.2e}")
+        assert e <= tol and torch.all(got[ch:] == -7.25)
+        del ws
 
 
 # ----------------------------------------------------------------------------- the other attentions / encoder in training mode (VERDICT r2 item 6)
