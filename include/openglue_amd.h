@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define OG_ABI_VERSION 13
+#define OG_ABI_VERSION 14
 
 #define OG_E_INVALID   (-1)  /* NULL pointer / non-positive size                         */
 #define OG_E_SHAPE     (-2)  /* unsupported shape (see og_check_shape)                   */
@@ -590,6 +590,51 @@ int og_superpoint_detect(int32_t batch, int32_t Hh, int32_t Wh, int32_t nms_kern
                          void* workspace_dev, void* stream);
 int og_superpoint_describe(int32_t batch, int32_t Hc, int32_t Wc, int32_t n, const int32_t* sel_idx, const float* sel_score,
                            int64_t sel_ld, const float* coarse_desc, float* lafs, float* scores, float* descriptors, void* stream);
+
+/* ABI v14 -- the reference's optimizer step: torch.optim.Adam + StepLR(step_size=1) stepped every iteration (models/matching_module.py:133-147)
+ * behind torch.nn.utils.clip_grad_norm_ (train.py:73 gradient_clip_val), fused into three launches whatever the number of parameters
+ * (csrc/optimizer.hip).  The caller owns three flat fp32 device buffers grad / exp_avg / exp_avg_sq of layout.total floats in which
+ * parameter i has the segment [offsets[i], offsets[i] + numel[i]); every offset is a multiple of 4, the padding between segments is zero and is
+ * never written.  The parameters themselves stay where they are (16-byte aligned device pointers).
+ *
+ * og_adam_layout (host arithmetic only): from the numel list, offsets [count] (may be NULL), the chunk map (may be NULL: sizes only;
+ *   else 2 * num_chunks int32, {parameter index, chunk index within the parameter} per update workgroup -- parameter i is cut into
+ *   ceil(numel[i] / OG_ADAM_CHUNK) chunks of OG_ADAM_CHUNK floats) and the sizes.  OG_E_INVALID for an empty list or a numel <= 0.
+ * og_adam_step: one step.  params: HOST array of the count parameter pointers (checked: NULL -> OG_E_INVALID, not 16-byte aligned ->
+ *   OG_E_ALIGN); table_dev: the same on the DEVICE, count rows of three 8-byte words {pointer, offset, numel} (layout.table_bytes);
+ *   chunk_map_dev: the chunk map on the device; workspace_dev: layout.workspace_bytes bytes, 8-byte aligned, whose first OG_ADAM_SCALARS
+ *   doubles are the scalars block below -- zero it once, it carries the step count from call to call (set OG_ADAM_STEP to resume).
+ *     clip != 0: adam_gradnorm_kernel (fp32 squares of the flat gradient summed in fp64, one partial per OG_ADAM_NORM_CHUNK floats, no
+ *       atomics), then adam_prepare_kernel: total_norm = sqrt(sum of the partials in a fixed order), clip_coef = min(1, max_norm /
+ *       (total_norm + 1e-6)).  clip == 0: no norm launch, total_norm = NaN, clip_coef = 1.
+ *     step += 1; lr_t = lr gamma^(step-1); step_size = lr_t / (1 - beta1^step); all scalar arithmetic in fp64.
+ *     adam_update_kernel, per element in fp32, every operation rounded on its own as torch's kernels round it:
+ *       g = clip_coef g; m = m + (1-beta1)(g - m); v = beta2 v + (1-beta2) g g; p = p - step_size m / (sqrt(v) / sqrt(1-beta2^step) + eps);
+ *       p, m, v are stored and g = 0 is written: the next backward accumulates into zeros.
+ *   Every parameter takes part in every step (a zero gradient is a gradient).  No host synchronisation, no copy, no atomics: results are
+ *   bit-identical from run to run. */
+#define OG_ADAM_CHUNK         4096
+#define OG_ADAM_NORM_CHUNK    8192
+#define OG_ADAM_SCALARS       8      /* doubles at the head of the workspace: */
+#define OG_ADAM_TOTAL_NORM    0      /*   gradient norm before clipping (NaN when clip == 0)   */
+#define OG_ADAM_CLIP_COEF     1
+#define OG_ADAM_STEP          2      /*   steps taken so far                                   */
+#define OG_ADAM_LR            3      /*   lr_t of the last step                                */
+#define OG_ADAM_STEP_SIZE     4
+#define OG_ADAM_INV_SQRT_BC2  5
+typedef struct og_adam_layout_t {
+    int64_t total;            /* floats of each flat buffer (multiple of 4)                    */
+    int64_t table_bytes;      /* device table: count rows of 24 bytes                          */
+    int64_t workspace_bytes;  /* scalars block + norm partials                                 */
+    int32_t num_chunks;       /* update workgroups = rows of the chunk map                     */
+    int32_t num_partials;     /* norm workgroups                                               */
+    int32_t chunk;            /* OG_ADAM_CHUNK                                                 */
+    int32_t reserved;
+} og_adam_layout_t;
+int og_adam_layout(int32_t count, const int64_t* numel, int64_t* offsets, int32_t* chunk_map, og_adam_layout_t* layout);
+int og_adam_step(int32_t count, const void* const* params, const void* table_dev, const int32_t* chunk_map_dev, int32_t num_chunks,
+                 int64_t total, float* grad, float* exp_avg, float* exp_avg_sq, double* workspace_dev, double lr, double gamma,
+                 double beta1, double beta2, double eps, int32_t clip, double max_norm, void* stream);
 
 #ifdef __cplusplus
 }

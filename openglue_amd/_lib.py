@@ -17,11 +17,13 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OPENGLUE_AMD_LIB") or os.path.join(HERE, "lib", "libopenglue_amd.so")   # override: A/B builds
 
-OG_ABI_VERSION = 13
+OG_ABI_VERSION = 14
 OG_FLAG_RESIDUAL, OG_FLAG_USE_OFFSET, OG_FLAG_NO_DESCRIPTORS, OG_FLAG_SIREN_ENCODER, OG_FLAG_LINEAR_ATTENTION = 1, 2, 4, 8, 16
 OG_FLAG_FAVOR_RELU = 32
 OG_MAX_HIDDEN = 8
 OG_MAX_RAGGED = 64
+OG_ADAM_CHUNK, OG_ADAM_NORM_CHUNK, OG_ADAM_SCALARS = 4096, 8192, 8
+OG_ADAM_TOTAL_NORM, OG_ADAM_CLIP_COEF, OG_ADAM_STEP, OG_ADAM_LR, OG_ADAM_STEP_SIZE, OG_ADAM_INV_SQRT_BC2 = range(6)
 OG_STAGES = ("encoder_input", "gemm_f32", "attention", "sinkhorn", "matches", "gemm_f16x3", "mlp_fused")
 
 _ERRORS = {-1: "OG_E_INVALID (null pointer / bad size)", -2: "OG_E_SHAPE (unsupported shape)",
@@ -75,6 +77,11 @@ class og_packed_layout_t(C.Structure):
                 ("enc_w", C.c_int64 * (OG_MAX_HIDDEN + 1)), ("enc_b", C.c_int64 * (OG_MAX_HIDDEN + 1))] + \
                [(k, C.c_int64) for k in ("layer0", "layer_stride", "o_wqkv", "o_bqkv", "o_w0", "o_b0", "o_w3", "o_b3",
                                          "wp", "bp", "alpha", "dustbin", "total", "o_scale", "scales", "o_wmlp", "o_wqkvs", "o_wqkvb")]
+
+
+class og_adam_layout_t(C.Structure):
+    _fields_ = [("total", C.c_int64), ("table_bytes", C.c_int64), ("workspace_bytes", C.c_int64), ("num_chunks", C.c_int32),
+                ("num_partials", C.c_int32), ("chunk", C.c_int32), ("reserved", C.c_int32)]
 
 
 # every symbol include/openglue_amd.h declares: name -> (restype, argtypes)
@@ -165,6 +172,9 @@ SYMBOLS = {
     "og_superpoint_dense": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_superpoint_detect": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _f, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "og_superpoint_describe": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "og_adam_layout": (C.c_int, [_i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(og_adam_layout_t)]),
+    "og_adam_step": (C.c_int, [_i32, C.POINTER(C.c_void_p), _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double,
+                               C.c_double, C.c_double, _i32, C.c_double, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
