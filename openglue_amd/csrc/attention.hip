@@ -620,15 +620,20 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
         }
     }
     const int64_t k_tile0 = (kv_row0 * a.ldk + h * DH) * 2, v_tile0 = (kv_row0 * a.ldv + h * DH) * 2;   // bytes, uniform
+    const int ntiles = (nk + KV_TILE - 1) / KV_TILE;
     // one tile = 8 DMA instructions per wave, issued in pairs (plane pair pp: 0 = K hi/lo, 1 = V hi/lo of piece i) so that
     // the main loop can spread them under its MFMA bursts: the vector-memory path takes 64 B/clk per CU, a burst of 8 per
     // wave right after the barrier stalls every wave of the workgroup for ~700 cycles (scripts/trace_attention.py)
-#ifndef OG_ATTN_ASMDMA
-#define OG_ATTN_ASMDMA 0      // 1 (experiment, round 3): scalar plane base + 32-bit lane offset in one asm block per (hi, lo) pair -- measured no gain (252 vs 249 us)
-#endif
-    // (scalar plane base + 32-bit lane offset) addressing, one asm block per (hi, lo) pair: the lane part is loop invariant except in
-    // the last tile (row clamp); as builtin calls every piece carried 64-bit per-lane address arithmetic on the vector ALU -- which
-    // shares its issue with the matrix pipe.
+    //
+    // Addressing: SCALAR plane base + ONE 32-bit lane offset, both instructions of a (hi, lo) pair in one asm block.
+    //   - the four plane bases (Kh, Kl, Vh, Vl) of the next tile to fetch live in SGPR pairs and advance once per tile by a scalar
+    //     64-bit add of KV_TILE rows (next_tile());
+    //   - the lane part is loop invariant: koffs / voffs, row (16 w + i RPI + rl) of the tile + the swizzled chunk, made once here;
+    //   - only the LAST tile of a problem can hold rows past the last key: its rows are clamped (and masked in the softmax), which
+    //     costs lane arithmetic -- so the clamp is a compile-time variant of the issue (CLAMP) that the steady-state loop never
+    //     instantiates (the loop fetches no last tile, see the driver below), made INSIDE the stagger branch of the issuing wave.
+    // As builtin calls every piece rebuilt a 64-bit per-lane address on the vector ALU -- 54 instructions per tile and wave, at every
+    // stagger position whether the wave issued there or not -- and the vector ALU shares its issue with the matrix pipe.
     unsigned koffs[NPI], voffs[NPI];
 #pragma unroll
     for (int i = 0; i < NPI; ++i) {
@@ -637,62 +642,64 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
         voffs[i] = (unsigned)(r * ldvb) + vsw;
         asm volatile("" : "+v"(koffs[i]), "+v"(voffs[i]));
     }
-    static_assert(!MX || !OG_ATTN_ASMDMA, "the MX form uses the builtin DMA path");
     [[maybe_unused]] auto sptr = [](const char* p) {
         const uint64_t v = (uint64_t)(uintptr_t)p;
         const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
         return reinterpret_cast<const char*>((uintptr_t)(((uint64_t)hi32 << 32) | lo));
     };
-    auto issue_pair = [&](int kt, auto BUF, auto I, auto PP) {
+    const char* pkh = reinterpret_cast<const char*>(a.kh) + k_tile0;      // tile 0; all uniform
+    const char* pkl = reinterpret_cast<const char*>(a.kl) + k_tile0;
+    const char* pvh = reinterpret_cast<const char*>(a.vh) + v_tile0;
+    const char* pvl = reinterpret_cast<const char*>(a.vl) + v_tile0;
+    const int64_t k_tile_step = (int64_t)KV_TILE * ldkb, v_tile_step = (int64_t)KV_TILE * ldvb;
+    [[maybe_unused]] auto next_tile = [&] { pkh += k_tile_step; pkl += k_tile_step; pvh += v_tile_step; pvl += v_tile_step; };
+    const int last_row = nk - 1 - (ntiles - 1) * KV_TILE;                 // last valid row of the last tile
+    [[maybe_unused]] const unsigned m0_wave = lds0_dma + (unsigned)(wave * RW * ROWB);        // LDS address of this wave's rows in plane 0 of buffer 0
+    // the (hi, lo) pair of piece i of plane pair pp into buffer b, from the tile the bases point at; over = rows this lane lies past the last key (CLAMP)
+    [[maybe_unused]] auto issue_pair = [&](auto BUF, auto I, auto PP, auto CLAMP, int over) {
         constexpr int b = decltype(BUF)::value, i = decltype(I)::value, pp = decltype(PP)::value;
-        const int key0 = kt * KV_TILE;
-        const int last = nk - 1 - key0;                  // rows past the last key are clamped (masked in the softmax)
-#if OG_ATTN_ASMDMA
         unsigned off = pp == 0 ? koffs[i] : voffs[i];
-        if (last < KV_TILE - 1) {                        // block-uniform: only the last tile of a problem
-            int r = wave * 16 + i * RPI + rl;
-            r = r < last ? r : last;
-            off = pp == 0 ? (unsigned)(r * ldkb) + ksw[i] : (unsigned)(r * ldvb) + vsw;
-        }
-        const int64_t o = pp == 0 ? k_tile0 + (int64_t)key0 * ldkb : v_tile0 + (int64_t)key0 * ldvb;       // uniform
-        const char* bh = sptr(reinterpret_cast<const char*>(pp == 0 ? a.kh : a.vh) + o);
-        const char* bl = sptr(reinterpret_cast<const char*>(pp == 0 ? a.kl : a.vl) + o);
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0_dma + b * BUFB + (wave * 16 + i * RPI) * ROWB + pp * 2 * PLANE);
-        asm volatile("s_mov_b32 m0, %3\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, %1\n\t"
-                     "s_add_u32 m0, m0, %4\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, %2"
-                     :: "v"(off), "s"(bh), "s"(bl), "s"(m0v), "n"(PLANE) : "memory");
-#else
-        int r = wave * 16 + i * RPI + rl;
-        r = r < last ? r : last;
-        // (an LDS-typed base cast once at kernel entry: a generic -> LDS cast at a call site the optimiser cannot see through emits an illegal
-        //  V_CMP against src_shared_base on this compiler)
-        __attribute__((address_space(3))) char* const dst = smem_lds + b * BUFB + (wave * 16 + i * RPI) * ROWB + pp * 2 * PLANE;
-        if constexpr (pp == 0) {
-            const int64_t o = k_tile0 + (int64_t)key0 * ldkb + (unsigned)(r * ldkb) + ksw[i];
-            __builtin_amdgcn_global_load_lds((og_glb_void*)(reinterpret_cast<const char*>(a.kh) + o), (og_lds_void*)(dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((og_glb_void*)(reinterpret_cast<const char*>(a.kl) + o), (og_lds_void*)(dst + PLANE), 16, 0, 0);
+        if constexpr (decltype(CLAMP)::value) off -= (unsigned)(over * (pp == 0 ? ldkb : ldvb));      // = min(row, last) * ld + chunk
+        const char* const bh = pp == 0 ? pkh : pvh;
+        const char* const bl = pp == 0 ? pkl : pvl;
+        [[maybe_unused]] const unsigned m0w = m0_wave;
+        if constexpr (MX) {
+            // (an LDS-typed base cast once at kernel entry: a generic -> LDS cast at a call site the optimiser cannot see through emits an illegal
+            //  V_CMP against src_shared_base on this compiler)
+            __attribute__((address_space(3))) char* const dst = smem_lds + b * BUFB + (wave * RW + i * RPI) * ROWB + pp * 2 * PLANE;
+            if constexpr (pp == 0) {
+                __builtin_amdgcn_global_load_lds((og_glb_void*)(bh + off), (og_lds_void*)(dst), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((og_glb_void*)(bl + off), (og_lds_void*)(dst + PLANE), 16, 0, 0);
+            } else {
+                __builtin_amdgcn_global_load_lds((og_glb_void*)(bh + off), (og_lds_void*)(dst), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((og_glb_void*)(bl + (off - vsw + vsw8[i & 1])), (og_lds_void*)(dst + PLANE), 16, 0, 0);
+            }
         } else {
-            const int64_t o = v_tile0 + (int64_t)key0 * ldvb + (unsigned)(r * ldvb) + vsw;
-            __builtin_amdgcn_global_load_lds((og_glb_void*)(reinterpret_cast<const char*>(a.vh) + o), (og_lds_void*)(dst), 16, 0, 0);
-            if constexpr (MX) {
-                const int64_t o8 = v_tile0 + (int64_t)key0 * ldvb + (unsigned)(r * ldvb) + vsw8[i & 1];
-                __builtin_amdgcn_global_load_lds((og_glb_void*)(reinterpret_cast<const char*>(a.vl) + o8), (og_lds_void*)(dst + PLANE), 16, 0, 0);
-            } else
-            __builtin_amdgcn_global_load_lds((og_glb_void*)(reinterpret_cast<const char*>(a.vl) + o), (og_lds_void*)(dst + PLANE), 16, 0, 0);
+            // M0 = the LDS address of the wave's first row of the piece; one wait state between a scalar write of M0 and the DMA instruction that reads it
+            asm volatile("s_add_u32 m0, %3, %4\n\t"
+                         "s_nop 0\n\t"
+                         "global_load_lds_dwordx4 %0, %1\n\t"
+                         "s_add_u32 m0, m0, %5\n\t"
+                         "s_nop 0\n\t"
+                         "global_load_lds_dwordx4 %0, %2"
+                         :: "v"(off), "s"(bh), "s"(bl), "s"(m0w), "n"(b * BUFB + i * RPI * ROWB + pp * 2 * PLANE), "n"(PLANE)
+                         : "memory", "scc");
         }
-#endif
     };
-    auto issue_tile = [&](int kt, auto BUF) {
+    [[maybe_unused]] auto issue_tile = [&](auto BUF, auto CLAMP) {
+        int over = 0;
+        if constexpr (decltype(CLAMP)::value) {
+            int ln = lane;
+            asm volatile("" : "+v"(ln));                 // opaque: the clamp is made HERE, by the wave that issues, not hoisted in front of the stagger branches
+            over = wave * RW + ln / LPR - last_row;      // piece i lies i RPI rows further down
+        }
         static_for<2 * NPI>([&](auto J) {
-            constexpr int j = decltype(J)::value;
-            issue_pair(kt, BUF, std::integral_constant<int, (j >> 1)>{}, std::integral_constant<int, (j & 1)>{});
+            constexpr int j = decltype(J)::value, i = j >> 1;
+            int o = over + i * RPI;
+            o = o > 0 ? o : 0;
+            issue_pair(BUF, std::integral_constant<int, i>{}, std::integral_constant<int, (j & 1)>{}, CLAMP, o);
         });
     };
-    const int ntiles = (nk + KV_TILE - 1) / KV_TILE;
     // pipelined form: one (hi, lo) pair of DMA instructions of tile kt, piece i, into the ring slot at byte offset slot_off (run-time: K slot (kt & 1) * 2 PLANE,
     // V slot 4 PLANE + (kt % 3) * 2 PLANE)
     [[maybe_unused]] auto pipe_dma = [&](int kt, auto I, auto PP, int slot_off) {
@@ -730,7 +737,11 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
                 pipe_dma(1, I, std::integral_constant<int, 1>{}, 6 * PLANE);
             }
         });
-    } else if (ntiles > 0) issue_tile(0, std::integral_constant<int, 0>{});
+    } else if (ntiles > 0) {
+        if (ntiles == 1) issue_tile(std::integral_constant<int, 0>{}, std::true_type{});       // tile 0 is also the last one
+        else issue_tile(std::integral_constant<int, 0>{}, std::false_type{});
+        next_tile();
+    }
 
     // ---- Q fragments (B operand): lane (query l31, k-group hi) holds Q[q][16c + 8hi + e] ----
     f16x8 qh[NCH], ql[NCH];
@@ -795,12 +806,15 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
 
     // MASKED: this tile may hold padded keys (only the last tile of a problem can).  A compile-time flag: with the mask as a
     // run-time branch the two sides of it merged the 32 score registers through register copies in EVERY tile.
-    auto tile_step = [&](int kt, auto BUF, auto MASKED) {
-        constexpr int b = decltype(BUF)::value;
-        constexpr bool masked = decltype(MASKED)::value;
+    // FETCH: what this step fetches behind its QK^T MFMAs -- 0: nothing (the last tile), 1: tile kt + 1, which is not the last one, -1: decided at
+    // run time by fk (0: nothing, 1: tile kt + 1, 2: tile kt + 1 which is the last one: clamped rows).  FIRST: tile 0, which sets the running max
+    // (always the slow path of the softmax).  The steady-state loop runs (unmasked, 1, not first) twice: the fast path, the rare rescale, nothing
+    // else; the steps around it (-1) keep the code small.
+    auto tile_step = [&](int kt, auto BUF, auto MASKED, auto FETCH, auto FIRST, int fk) {
+        constexpr int b = decltype(BUF)::value, fetch = decltype(FETCH)::value;
+        constexpr bool masked = decltype(MASKED)::value, first = decltype(FIRST)::value;
         const int key0 = kt * KV_TILE;
         OG_TP(0);
-        const bool more = kt + 1 < ntiles;
         OG_TP(1);
 
         // One LDS read per call, so that the reads of the NEXT chunk / group are slotted between the MFMAs of the current one:
@@ -872,11 +886,19 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
                     // instruction per CU; when all waves of the workgroup issue at the same point each instruction queues behind
                     // the others' (~125 cycles each in the trace), one wave at a time pays only its own service time.
                     if constexpr (m == 4) {
-                        if (more && wave % NCH == c) issue_tile(kt + 1, std::integral_constant<int, b ^ 1>{});
+                        if constexpr (fetch == 1) {
+                            if (wave % NCH == c) issue_tile(std::integral_constant<int, b ^ 1>{}, std::false_type{});
+                        } else if constexpr (fetch == -1) {
+                            if (fk != 0 && wave % NCH == c) {
+                                if (fk == 2) issue_tile(std::integral_constant<int, b ^ 1>{}, std::true_type{});
+                                else issue_tile(std::integral_constant<int, b ^ 1>{}, std::false_type{});
+                            }
+                        }
                         fence();
                     }
                 });
             });
+            if constexpr (fetch != 0) next_tile();          // scalar: every wave, wherever it issued
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb) {
                 if (masked && key0 + KV_TILE > nk) {        // only the last tile can hold padded keys (block-uniform)
@@ -947,31 +969,21 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
             tsum = (ps0 + ps1) + (ps2 + ps3);
 #endif
         };
-        bool redo = kt == 0;                              // the first tile replaces the arbitrary start value of m_run
-#if !OG_ATTN_MAXFIRST
-        if (!redo) {
-            exp_split();
-            redo = __any(!(tsum <= (MX ? 256.f : SUM_LIMIT)));           // wave-uniform; catches inf and NaN too (MX: every p inside e4m3's 448)
-        }
-#endif
         float mt = 0.f;
-        if (OG_ATTN_MAXFIRST || redo) {
+        auto tile_max = [&] {
             mt = s[0][0];
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) mt = fmaxf(mt, s[kb][r]);
             mt = fmaxf(mt, __shfl_xor(mt, 32, 64));      // max of s - m_run over the tile; finite: every tile holds >= 1 valid key
-#if OG_ATTN_MAXFIRST
-            redo = redo || __any(mt > RESCALE_THR);
-#endif
-        }
-        if (redo) {
-            const float delta = kt == 0 ? mt : fmaxf(mt, 0.f);       // new running max = m_run + delta
+        };
+        auto rescale = [&] {                              // the first tile replaces the arbitrary start value of m_run
+            const float delta = first ? mt : fmaxf(mt, 0.f);         // new running max = m_run + delta
             m_run += delta;
 #pragma unroll
             for (int r = 0; r < 16; ++r) negm[r] = -m_run;
-            if (kt > 0) {
+            if constexpr (!first) {
                 const float alpha = __builtin_amdgcn_exp2f(-delta);  // rows that did not grow: 2^0 = 1
                 l_run *= alpha;
 #pragma unroll
@@ -983,8 +995,23 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[kb][r] -= delta;
+        };
+#if OG_ATTN_MAXFIRST
+        tile_max();
+        if (first || __any(mt > RESCALE_THR)) rescale();
+        exp_split();
+#else
+        // ONE instance of the exponentials, entered a second time after the rescale (at most once: the scores are <= 0 then): as two instances -- fast
+        // path, slow path -- the register allocator gave their 32 results different registers in one of the two unrolled bodies and copied 16 of them
+        // on the fast side of the join in every tile.
+        int pass = first ? 1 : 0;
+#pragma nounroll
+        for (;; ++pass) {
+            if (pass == 1) { tile_max(); rescale(); }
+            exp_split();
+            if (pass == 1 || !__any(!(tsum <= (MX ? 256.f : SUM_LIMIT)))) break;      // wave-uniform; catches inf and NaN too (MX: every p inside e4m3's 448)
         }
-        if (OG_ATTN_MAXFIRST || redo) exp_split();
+#endif
         l_run += tsum;
         f16x8 pf[2][2], pl[2][2];
 #pragma unroll
@@ -1063,7 +1090,7 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
         });
 
         OG_TP(4);
-        if (kt + 1 < ntiles) {
+        if (fetch == 1 || (fetch == -1 && fk != 0)) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // my pieces of tile t+1 landed
             OG_TP(5);
             __syncthreads();                                      // ... everybody's did, and everybody is done with tile t
@@ -1395,18 +1422,22 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
         if (t <= ntiles) step(t, sA, pfA, plA, sB, pfB, plB);
     } else
     if (ntiles > 0) {
+        // Tile 0 (buffer 0) sets the running max; then PAIRS of tiles (buffers 1, 0) that are not the last one and fetch no last tile -- no mask, no
+        // row clamp, no first-tile case: nothing but the fast path -- and the one to three tiles that are left, each in the variant it needs.
         using B0 = std::integral_constant<int, 0>; using B1 = std::integral_constant<int, 1>;
-        int kt = 0;
-        for (; kt + 2 < ntiles; kt += 2) {                 // pairs of tiles that are not the last one: no mask code at all
-            tile_step(kt, B0{}, std::false_type{});
-            tile_step(kt + 1, B1{}, std::false_type{});
+        using F0 = std::integral_constant<int, 0>; using F1 = std::integral_constant<int, 1>; using FR = std::integral_constant<int, -1>;
+        using Y = std::true_type; using N = std::false_type;
+        tile_step(0, B0{}, Y{}, FR{}, Y{}, ntiles == 1 ? 0 : ntiles == 2 ? 2 : 1);
+        int kt = 1;
+        for (; kt + 3 < ntiles; kt += 2) {
+            tile_step(kt, B1{}, N{}, F1{}, N{}, 1);
+            tile_step(kt + 1, B0{}, N{}, F1{}, N{}, 1);
         }
-        if (kt + 1 < ntiles) {
-            tile_step(kt, B0{}, std::false_type{});
-            tile_step(kt + 1, B1{}, std::true_type{});
-        } else {
-            tile_step(kt, B0{}, std::true_type{});
-        }
+        const int left = ntiles - kt;                      // 0 (one tile in all) .. 3
+        if (left >= 2) { tile_step(kt, B1{}, N{}, FR{}, N{}, left == 2 ? 2 : 1); ++kt; }
+        if (left == 3) { tile_step(kt, B0{}, N{}, FR{}, N{}, 2); ++kt; }
+        if (left == 2) tile_step(kt, B0{}, Y{}, F0{}, N{}, 0);
+        else if (left & 1) tile_step(kt, B1{}, Y{}, F0{}, N{}, 0);
     }
 
     if constexpr (KS == 2) {
