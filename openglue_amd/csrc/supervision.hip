@@ -13,10 +13,14 @@
 //  * og_criterion_forward / _backward -- utils/losses.py `criterion`: the NLL over `scores` (dustbins included) and, with
 //    a margin, the triplet / hinge metric loss on the cosine distance of the context descriptors:
 //      norm_kernel       1 / max(|x|, 1e-12) per keypoint (F.normalize), on the channel-first [B][D][n] tensors as they lie
-//      gram_kernel       cos = a.b on exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), dist = 0.5 (1 - cos); the epilogue does the
+//      gram_kernel       cos = a.b on exact-fp32 MFMA (v_mfma_f32_32x32x2_f32), dist = 0.25 (|a^|^2 + |b^|^2) - 0.5 cos, which is
+//                        0.5 (1 - cos) bit for bit unless a descriptor is all zero (a^ = 0: utils/misc.py's
+//                        0.25 |a^ - b^|^2 is then 0.25, not 0.5); the epilogue does the
 //                        four argmins (row / column, over dist and over dist with the positives gt0[i] == j at +inf) and
 //                        merges them across workgroups with packed 64-bit atomicMin on (orderable value, index)
-//      pair_loss_kernel  one workgroup per pair: the per-pair means of the NLL and of the hinge terms, fixed-order sums
+//      pair_loss_kernel  one workgroup per pair: the per-pair means of the NLL and of the hinge terms, fixed-order sums; a
+//                        masked minimum of +inf (the positive is the only entry of its row / column) gives the term
+//                        `margin`, as the reference's argmin of an all-inf line does (it gathers d_an = d_ap)
 //      finish_kernel     the sums over pairs in pair order, / B  -> loss, metric_loss (bit-identical from run to run)
 //    backward: nll_grad_kernel writes the dense grad_scores the Sinkhorn backward takes; metric_scatter_kernel adds
 //    0.5 c (a^ - b^) for the O(M + N) distance entries that carry a gradient (float atomics: one row can be the hardest
@@ -315,6 +319,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ d0,
     __shared__ __attribute__((aligned(16))) float As[GK * GLD];
     __shared__ __attribute__((aligned(16))) float Bs[GK * GLD];
     __shared__ float sinv0[GT], sinv1[GT];
+    __shared__ float sq0[GT], sq1[GT];                    // 0.25 |x^|^2: 0.25, or 0 for an all-zero descriptor (F.normalize's clamp)
     __shared__ int spos[GT];
     const int b = blockIdx.z;
     const int m0 = blockIdx.y * GT, n0 = blockIdx.x * GT;
@@ -325,11 +330,13 @@ __global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ d0,
     if (tid < GT) {
         const int i = m0 + tid;
         sinv0[tid] = i < m ? w.inv0[(int64_t)b * m + i] : 0.f;
+        sq0[tid] = sinv0[tid] == 1.f / kEpsNorm ? 0.f : 0.25f;
         const int64_t g = i < m ? gt0[(int64_t)b * m + i] : -1;
         spos[tid] = (g >= 0 && g < n) ? (int)g : -1;
     } else if (tid < 2 * GT) {
         const int j = n0 + tid - GT;
         sinv1[tid - GT] = j < n ? w.inv1[(int64_t)b * n + j] : 0.f;
+        sq1[tid - GT] = sinv1[tid - GT] == 1.f / kEpsNorm ? 0.f : 0.25f;
     }
     f32x16 acc;
 #pragma unroll
@@ -363,8 +370,8 @@ __global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ d0,
         const int rl = wm * 32 + mfma32_row(r, lane);
         const int i = m0 + rl;
         const bool ok = jok && i < m;
-        const float cosv = acc[r] * sinv0[rl] * sinv1[cl];
-        const float d = 0.5f * (1.f - cosv);
+        // one rounding of 0.5 - 0.5 (acc inv0) inv1, spelled out so that it does not hang on the compiler's contraction
+        const float d = fmaf(-0.5f * (acc[r] * sinv0[rl]), sinv1[cl], sq0[rl] + sq1[cl]);
         const bool positive = spos[rl] == j;
         if (ok && positive) w.dap[(int64_t)b * m + i] = d;
         const float dm = positive ? __builtin_huge_valf() : d;
@@ -435,7 +442,11 @@ __global__ __launch_bounds__(256) void pair_loss_kernel(const float* __restrict_
                 const float dap = w.dap[(int64_t)b * m + i];
                 const float an0 = sv_unorderable((unsigned)(w.rowm[(int64_t)b * m + i] >> 32));
                 const float an1 = sv_unorderable((unsigned)(w.colm[(int64_t)b * n + g] >> 32));
-                hm += fmaxf(dap - an0 + margin, 0.f) + fmaxf(dap - an1 + margin, 0.f);
+                // +inf: no other candidate in that row / column; the backward leaves such a term without gradient
+                // (select the argument, then one fmaxf: with fmaxf in both arms of the select, ROCm 7.2's gfx950 instruction selection crashes)
+                const float inf = __builtin_huge_valf();
+                const float t0 = an0 == inf ? margin : dap - an0 + margin, t1 = an1 == inf ? margin : dap - an1 + margin;
+                hm += fmaxf(t0, 0.f) + fmaxf(t1, 0.f);
             }
         } else if (g == -1) {
             ++c0;

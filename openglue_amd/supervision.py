@@ -166,7 +166,9 @@ def criterion(y_true: Dict[str, torch.Tensor], y_pred: Dict[str, torch.Tensor], 
     """utils/losses.py:7-52 on the GPU: {'loss': the NLL over `scores` (dustbins included), 'metric_loss': the triplet / hinge
     loss on the cosine distance of `context_descriptors0/1` (a zero tensor when `margin` is None, and no Gram matrix is
     formed)}.  Gradients flow to `scores` and, with a margin, to both descriptor tensors.  Loss values are bit-identical from
-    run to run; the descriptor gradients are float-atomic sums."""
+    run to run; the descriptor gradients are float-atomic sums.  Two degenerate inputs follow the reference too: an all-zero
+    descriptor (F.normalize clamps it to 0) is at distance 0.25 from every other descriptor and 0 from another zero one, and a
+    match that is the only entry of its row or column (M == 1 or N == 1) contributes exactly `margin`, without gradient."""
     scores = y_pred["scores"]
     if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
         raise RuntimeError("scores: expected a tensor on the GPU; openglue_amd has no CPU path")

@@ -1,11 +1,14 @@
 """CPU checks of the training supervision (openglue_amd.supervision): the float64 restatement in tests/supervision_ref.py against the
-reference's own labels and losses stored in tests/golden/supervision.npz, the apply_thresholds rules, and the wrappers' refusals."""
+reference's own labels and losses stored in tests/golden/supervision.npz, the apply_thresholds rules, and the wrappers' refusals;
+the seeded criterion cases of tests/criterion_cases.py: the branches each one takes, and the restatement against the reference's
+results on them (tests/golden/criterion.npz)."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from tests import criterion_cases as cc
 from tests import supervision_ref as ref
 from tests.util import parity_note
 
@@ -13,6 +16,9 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 Z = np.load(os.path.join(GOLDEN, "supervision.npz"))
 GT_CASES = ("persp", "depthkp", "depthmap", "quirk")
 POS, NEG = (float(v) for v in Z["gt_thresholds"])
+ZC = np.load(os.path.join(GOLDEN, "criterion.npz"))
+CRIT_CASES = {cc.case_name(s): (lambda s=s: cc.regular_case(s)) for s in cc.REGULAR}
+CRIT_CASES.update({f"single_m{m}_n{n}": (lambda m=m, n=n: cc.single_case(m, n)) for m, n in cc.SINGLE})
 
 
 def gt_case(name, device="cpu"):
@@ -107,6 +113,54 @@ def test_restatement_reproduces_reference_criterion(D, margin):
         for got, key in ((a.grad, "grad_desc0"), (b.grad, "grad_desc1")):
             w = Z[f"{name}_{key}"]
             assert np.abs(got.numpy() - w).max() < 1e-5 * np.abs(w).max(), key
+
+
+@pytest.mark.parametrize("shape", list(cc.REGULAR), ids=cc.case_name)
+def test_criterion_cases_take_every_hinge_branch(shape):
+    """Every regular case has active and inactive terms in all four hinge families (the smallest one apart), no hinge argument
+    and no argmin gap within fp32 rounding of a switch."""
+    _, a, b, g0, g1 = cc.regular_case(shape)
+    cen = cc.census(a, b, g0, g1)
+    print(f"[{cc.case_name(shape)}] {cen['counts']} min |hinge| {cen['min_hinge']:.3g} min gap {cen['min_gap']:.3g}")
+    assert cc.regular_case_ok(shape, cen) == []
+    assert int((g0 == -2).sum()) > 0 and int((g1 == -2).sum()) > 0
+    if shape[0] > 1:
+        assert int((g0[-1] >= 0).sum()) == 0                          # the last pair has no match
+    if shape[0] > 2:
+        assert int((g1[1] == -1).sum()) == 0 or int((g0[1] == -1).sum()) == 0      # pair 1: one image without unmatched keypoints
+
+
+def test_tie_and_zero_cases_are_what_they_claim():
+    for ignore in (False, True):
+        cc.tie_case_ok(cc.tie_case(ignore))
+    _, a, b, g0, g1, iz, jz = cc.zero_case()
+    assert g0[0, iz] == -1 and g1[0, jz] >= 0 and float(a[0, :, iz].abs().max()) == 0.0 and float(b[0, :, jz].abs().max()) == 0.0
+    cen = cc.census(a, b, g0, g1)
+    assert cen["min_hinge"] >= cc.MIN_HINGE and cen["min_gap"] >= cc.MIN_GAP
+    # the zero columns are chosen: each other's nearest neighbour at distance 0, and a negative of other keypoints at 0.25
+    assert [0, iz, jz] in cen["winners"]["unmatched0"].tolist() and [0, jz, iz] in cen["winners"]["triplet10"].tolist()
+    assert sum(int((cen["winners"][f][:, 2] == k).sum()) for f, k in (("triplet01", jz), ("triplet10", iz))) > 2
+
+
+@pytest.mark.parametrize("name", list(CRIT_CASES))
+@pytest.mark.parametrize("margin", (None, cc.MARGIN))
+def test_restatement_reproduces_reference_criterion_cases(name, margin):
+    key = f"{name}_{'none' if margin is None else 'margin'}"
+    got = cc.reference64(CRIT_CASES[name](), margin)
+    for k in ("loss", "metric_loss"):
+        assert abs(got[k] - float(ZC[f"{key}_{k}"])) <= 1e-5 * abs(float(ZC[f"{key}_{k}"])), k
+    if name.startswith("single") and margin is not None:
+        m, n = (int(t[1:]) for t in name.split("_")[1:])
+        _, a, b, g0, g1 = CRIT_CASES[name]()
+        cen = cc.census(a, b, g0, g1)
+        lone = ([cen["args"]["triplet01"]] if n == 1 else []) + ([cen["args"]["triplet10"]] if m == 1 else [])
+        assert lone and all(float(t) == cc.MARGIN for t in lone)      # d_an == d_ap: the term is the margin
+    for k in ("grad_scores", "grad_desc0", "grad_desc1"):
+        if got[k] is None:
+            assert f"{key}_{k}" not in ZC
+            continue
+        want = ZC[f"{key}_{k}"]
+        assert np.abs(got[k] - want).max() <= 1e-5 * np.abs(want).max(), k
 
 
 def test_wrappers_reject_cpu_tensors_and_unknown_transformations():
