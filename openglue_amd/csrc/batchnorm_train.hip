@@ -6,9 +6,12 @@
 //     running_mean = (1 - mom) running_mean + mom mean        running_var = (1 - mom) running_var + mom var * T / (T - 1)
 // (torch.nn.functional.batch_norm semantics).  Eval mode needs none of this: the running statistics are folded into the next
 // 1x1 conv at pack time (api.hip).
-// HBM-bound, three passes over x: (1) per-row-slab partial sums of (x - k) and (x - k)^2 with k = x[0][c] (a per-channel shift
-// removes the cancellation of E x^2 - (E x)^2 for channels whose mean dominates their spread), coalesced along the channel
-// axis; (2) one block folds the partials in double, updates the running statistics and emits scale = w * invstd,
+// HBM-bound, three passes over x: (1) per row slab and channel (mean, M2 = sum (x - mean)^2), coalesced along the channel axis: every
+// lane sums (x - p) and (x - p)^2 over its 8 rows about the FIRST row it reads (a shift removes the cancellation of E x^2 - (E x)^2 for
+// channels whose mean dominates their spread; with one pivot per lane a row that is not typical of its channel -- a ReLU zero in a
+// channel that sits at 10 +- 1e-3 -- costs its own 8 rows their shift, not the whole channel: whichever row is the pivot, the rounding of
+// a group of n rows is ~ n eps (p - mean)^2 against the (p - mean)^2 that the pivot itself adds to M2), the waves are merged with Chan's
+// pairwise formula; (2) one block folds the slabs' (mean, M2) in double, updates the running statistics and emits scale = w * invstd,
 // shift = b - mean * scale (+ mean / invstd for a later backward); (3) y = x * scale + shift, 16 bytes per lane.
 #include "og_common.h"
 
@@ -19,7 +22,7 @@ constexpr int BN_ROWS_PER_BLOCK = 32;       // rows folded by one block of pass 
 
 // Pass 1.  grid (ceil(rows / BN_ROWS_PER_BLOCK), ceil(C / 256)), 256 threads = 4 waves; a lane owns FOUR channels (one 16-byte load per row: a wave
 // reads 1 KB of a row), wave w the rows r0 + w, r0 + w + 4, ...; the waves meet in LDS in wave order.  part[(blk * C + c) * 2 + {0, 1}].
-// F(lane's 4 values of this row, lane's 4 channels) -> the two terms to accumulate
+// The backward's form: plain sums.  F(lane's 4 values of this row, lane's 4 channels) -> the two terms to accumulate
 template <class F>
 __device__ __forceinline__ void bn_fold_rows(int64_t rows, int C, float* __restrict__ part, F term) {
     __shared__ f32x4 red[2][3][64];
@@ -46,33 +49,68 @@ __device__ __forceinline__ void bn_fold_rows(int64_t rows, int C, float* __restr
     *reinterpret_cast<f32x4*>(dst + 4) = f32x4{s1[2], s2[2], s1[3], s2[3]};
 }
 
+// The forward's form: part = (mean, M2) of the slab.  Rows of wave w in a slab of L rows: (L - w + 3) / 4.
 __global__ __launch_bounds__(256) void bn_partial_kernel(const float* __restrict__ x, int64_t ldx, int64_t rows, int C, float* __restrict__ part) {
-    const int c0 = blockIdx.y * 256 + (threadIdx.x & 63) * 4;
-    const f32x4 k = c0 < C ? *reinterpret_cast<const f32x4*>(x + c0) : f32x4{0.f, 0.f, 0.f, 0.f};      // shift: row 0 of the channel
-    bn_fold_rows(rows, C, part, [&](int64_t r, int c, f32x4& s1, f32x4& s2) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + r * ldx + c);
+    __shared__ f32x4 red[2][3][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = blockIdx.y * 256 + lane * 4;
+    const int64_t r0 = (int64_t)blockIdx.x * BN_ROWS_PER_BLOCK;
+    const int L = (int)(r0 + BN_ROWS_PER_BLOCK < rows ? BN_ROWS_PER_BLOCK : rows - r0);
+    const int nl = (L - wave + 3) >> 2;                         // 0 for a wave without a row (L >= 1, wave <= 3)
+    f32x4 mean{0.f, 0.f, 0.f, 0.f}, m2{0.f, 0.f, 0.f, 0.f};
+    if (c < C && nl) {
+        const float* row = x + (r0 + wave) * ldx + c;
+        const f32x4 p = *reinterpret_cast<const f32x4*>(row);   // the lane's pivot: its first row
+        f32x4 s1{0.f, 0.f, 0.f, 0.f}, s2{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int i = 1; i < nl; ++i) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(row + (int64_t)i * 4 * ldx);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float d = v[e] - p[e];
+                s1[e] += d;
+                s2[e] = fmaf(d, d, s2[e]);
+            }
+        }
+        const float inv = 1.f / (float)nl;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const float d = v[e] - k[e];
-            s1[e] += d;
-            s2[e] = fmaf(d, d, s2[e]);
+            mean[e] = p[e] + s1[e] * inv;
+            m2[e] = fmaxf(s2[e] - s1[e] * s1[e] * inv, 0.f);
         }
-    });
+    }
+    if (wave) { red[0][wave - 1][lane] = mean; red[1][wave - 1][lane] = m2; }
+    __syncthreads();
+    if (wave || c >= C) return;
+    float na = (float)nl;                                       // wave 0 always has a row
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {                               // Chan: M2 = M2_a + M2_b + (mean_b - mean_a)^2 n_a n_b / n; an empty wave adds nothing
+        const float nb = (float)((L - w + 3) >> 2), n = na + nb, f = nb / n;
+        const f32x4 mb = red[0][w - 1][lane], qb = red[1][w - 1][lane];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float d = mb[e] - mean[e];
+            mean[e] += d * f;
+            m2[e] += qb[e] + d * d * (na * f);
+        }
+        na = n;
+    }
+    float* dst = part + ((int64_t)blockIdx.x * C + c) * 2;
+    *reinterpret_cast<f32x4*>(dst) = f32x4{mean[0], m2[0], mean[1], m2[1]};
+    *reinterpret_cast<f32x4*>(dst + 4) = f32x4{mean[2], m2[2], mean[3], m2[3]};
 }
 
 // The per-channel fold of the partials, in double: 64 channels per block, the four waves take the slabs i = w, w + 4, ... and meet in LDS in wave order
-// (one thread per channel walking every slab was fine at 32 slabs; there are 256 now).  -> (s1, s2) in the threads of wave 0, others return false.
-__device__ __forceinline__ bool bn_fold_partials(const float* __restrict__ part, int nblk, int C, int c, double& s1, double& s2) {
+// (one thread per channel walking every slab was fine at 32 slabs; there are 256 now).  F(slab, its two floats) -> the two terms to accumulate.
+// -> (s1, s2) in the threads of wave 0, others return false.
+template <class F>
+__device__ __forceinline__ bool bn_fold_partials(const float* __restrict__ part, int nblk, int C, int c, double& s1, double& s2, F term) {
     __shared__ double red[2][3][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     s1 = 0.0; s2 = 0.0;
     if (c < C) {
 #pragma unroll 4
-        for (int i = wave; i < nblk; i += 4) {
-            const float2 v = *reinterpret_cast<const float2*>(part + ((int64_t)i * C + c) * 2);
-            s1 += (double)v.x;
-            s2 += (double)v.y;
-        }
+        for (int i = wave; i < nblk; i += 4) term(i, *reinterpret_cast<const float2*>(part + ((int64_t)i * C + c) * 2), s1, s2);
     }
     if (wave) { red[0][wave - 1][lane] = s1; red[1][wave - 1][lane] = s2; }
     __syncthreads();
@@ -82,17 +120,24 @@ __device__ __forceinline__ bool bn_fold_partials(const float* __restrict__ part,
     return true;
 }
 
-// grid ceil(C / 64), 256 threads
-__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ x, const float* __restrict__ part, int nblk, int64_t rows, int C,
+// grid ceil(C / 64), 256 threads.  The slabs' (mean_i, M2_i) about K = the mean of slab 0, n_i from the slab index: in double the shift is a
+// courtesy (the means are float32 values: mean_i - K is exact), sum n_i (mean_i - K) and sum M2_i + n_i (mean_i - K)^2 are Chan's merge of all slabs.
+__global__ __launch_bounds__(256) void bn_finalize_kernel(const float* __restrict__ part, int nblk, int64_t rows, int C,
                                                           const float* __restrict__ w, const float* __restrict__ b, float eps, float momentum,
                                                           float* __restrict__ running_mean, float* __restrict__ running_var,
                                                           float* __restrict__ scale_shift, float* __restrict__ save_mean, float* __restrict__ save_invstd) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+    const double K = c < C ? (double)part[c * 2] : 0.0;
+    const double n_last = (double)(rows - (int64_t)(nblk - 1) * BN_ROWS_PER_BLOCK);
     double s1, s2;
-    if (!bn_fold_partials(part, nblk, C, c, s1, s2)) return;
+    if (!bn_fold_partials(part, nblk, C, c, s1, s2, [&](int i, float2 v, double& a1, double& a2) {
+            const double ni = i + 1 < nblk ? (double)BN_ROWS_PER_BLOCK : n_last, d = (double)v.x - K;
+            a1 += ni * d;
+            a2 += (double)v.y + ni * d * d;
+        })) return;
     const double n = (double)rows;
-    const double dm = s1 / n;                                   // mean - k
-    const double mean = (double)x[c] + dm;
+    const double dm = s1 / n;                                   // mean - K
+    const double mean = K + dm;
     double var = s2 / n - dm * dm;                              // biased
     if (var < 0.0) var = 0.0;
     const double invstd = 1.0 / sqrt(var + (double)eps);
@@ -146,7 +191,7 @@ extern "C" int og_batchnorm_train_forward(const float* x, int64_t ldx, int64_t r
     float* part = reinterpret_cast<float*>(workspace);
     float* scale_shift = part + (int64_t)nblk * channels * 2;
     hipLaunchKernelGGL(bn_partial_kernel, dim3(nblk, (channels + 255) / 256), dim3(256), 0, st, x, ldx, rows, channels, part);
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((channels + 63) / 64), dim3(256), 0, st, x, part, nblk, rows, channels, weight, bias, eps, momentum,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((channels + 63) / 64), dim3(256), 0, st, part, nblk, rows, channels, weight, bias, eps, momentum,
                        running_mean, running_var, scale_shift, save_mean, save_invstd);
     const int64_t n4 = rows * (channels / 4);
     hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, x, ldx, rows, channels / 4, scale_shift, y, ldy);
@@ -184,7 +229,7 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* __res
                                                               float* __restrict__ coef) {
     const int c = blockIdx.x * 64 + (threadIdx.x & 63);
     double s1, s2;
-    if (!bn_fold_partials(part, nblk, C, c, s1, s2)) return;
+    if (!bn_fold_partials(part, nblk, C, c, s1, s2, [](int, float2 v, double& a1, double& a2) { a1 += (double)v.x; a2 += (double)v.y; })) return;
     if (dbias) dbias[c] = (float)s1;
     if (dweight) dweight[c] = (float)s2;
     coef[c] = (w ? w[c] : 1.f) * invstd[c];
