@@ -1,7 +1,12 @@
-"""Two images to matches on the GPU: SuperPointNetBn -> OpenGlueMatcher(SuperGlue), as the reference's inference.py does, on a
-synthetic homography pair with seeded weights.  Prints the shapes and the time per stage.
+"""Two images to verified matches on the GPU: SuperPointNetBn -> OpenGlueMatcher(SuperGlue) -> find_fundamental, the whole of the
+reference's inference.py run_inference, on a synthetic homography pair with seeded weights.  Prints the shapes and the time per stage.
+The pair is related by a homography, which is degenerate for a fundamental matrix (a family of F fits it equally well): the inlier
+count is shown, the accuracy of the stage is the business of tests/test_gpu_geometry.py.
 
-    python examples/match_images.py [--size 480x640] [--keypoints 2048]
+    python examples/match_images.py [--size 480x640] [--keypoints 2048] [--match-threshold 0.2]
+
+The seeded weights are not trained: at the reference's threshold of 0.2 they may leave no match at all, and the last stage then
+times its four launches on an empty pair.  --match-threshold 0 keeps every mutual best match and gives the stage real work.
 """
 import argparse
 import os
@@ -13,6 +18,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from examples.openglue_matcher import OpenGlueMatcher  # noqa: E402
 from openglue_amd import synthetic as syn  # noqa: E402
+from openglue_amd.geometry import find_fundamental  # noqa: E402
 from openglue_amd.superglue import SuperGlue  # noqa: E402
 from openglue_amd.superpoint import SuperPointNetBn  # noqa: E402
 
@@ -21,6 +27,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", default="480x640")
     ap.add_argument("--keypoints", type=int, default=2048)
+    ap.add_argument("--match-threshold", type=float, default=0.2)
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split("x"))
     dev = torch.device("cuda:0")
@@ -33,10 +40,11 @@ def main():
     sg = SuperGlue(cfg).eval()
     sg.load_state_dict(syn.make_state_dict(cfg, seed=0))
     sg = sg.to(dev)
-    matcher = OpenGlueMatcher(sp, sg, {"superglue": {"laf_to_sideinfo_method": "none"}, "inference": {"match_threshold": 0.2}})
+    matcher = OpenGlueMatcher(sp, sg, {"superglue": {"laf_to_sideinfo_method": "none"}, "inference": {"match_threshold": a.match_threshold}})
     data = {"image0": img0.to(dev), "image1": img1.to(dev)}
     for _ in range(2):                      # warm-up: packing, allocator
         out = matcher(data)
+        find_fundamental(out["keypoints0"], out["keypoints1"])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     lafs, _, _ = sp(torch.cat([data["image0"], data["image1"]]))
@@ -45,8 +53,12 @@ def main():
     out = matcher(data)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
+    F, inliers = find_fundamental(out["keypoints0"], out["keypoints1"])      # cv2.findFundamentalMat(..., USAC_MAGSAC, 1.0, 0.999, 100000)
+    torch.cuda.synchronize()
+    t3 = time.perf_counter()
     print(f"{H}x{W}: {lafs.shape[1]} keypoints per image, {out['keypoints0'].shape[0]} matches")
     print(f"SuperPoint on both images {1e3 * (t1 - t0):.2f} ms; images -> matches {1e3 * (t2 - t1):.2f} ms")
+    print(f"fundamental matrix: {int(inliers.sum())} inliers of {inliers.shape[0]} matches, {1e3 * (t3 - t2):.2f} ms")
 
 
 if __name__ == "__main__":

@@ -560,6 +560,30 @@ int og_relative_pose(int32_t batch, int32_t m, int32_t n, const float* keypoints
                      int64_t pair_offset, float* error, float* R_pred, float* t_pred, uint8_t* inliers,
                      int32_t* num_inliers, void* workspace_dev, void* stream);
 
+/* Uncalibrated geometric verification (csrc/geometry.hip): what inference.py takes from cv2.findFundamentalMat.  Added to ABI v14
+ * without a version bump: three new entries, nothing existing changes.  Pairs in the layout of the metrics above (keypoints in
+ * pixels, matches0 with the same validity rule); x1^T F x0 = 0 with x0 from keypoints0.
+ *
+ * og_fundamental_7pt: the seven-point minimal solver, fp64.  x0, x1 [count][7][2] correspondences with coordinates of order 1 (e.g.
+ *   Hartley-normalised) -> F [count][3][9] (row-major, unit Frobenius norm, in ascending order of the cubic's root, the root at infinity
+ *   last; the slots past num_solutions[p] are zero) and num_solutions [count] int32 (0..3).  A model is kept when the seven
+ *   constraints and det F hold to 1e-9.  One kernel, no workspace.  OG_E_INVALID for count <= 0 or count > 2^30.
+ * og_fundamental_matrix: per pair, Hartley normalisation of the valid matches (fp64), `hypotheses` samples of 7 distinct matches drawn
+ *   by the counter-based hash of (seed, pair_offset + b, hypothesis) as og_relative_pose draws its 5, every solution scored by the
+ *   squared Sampson error in pixels^2 <= threshold^2 (fp32); most inliers win, the lowest (hypothesis, solution) on ties.  Then
+ *   `refine` rounds (0: none) of a normalised eight-point least-squares fit to the current inliers with rank 2 enforced, each kept if
+ *   it has no fewer inliers, skipped below 8 inliers.  F [B][3][3] fp64 in pixels, unit Frobenius norm, largest entry positive;
+ *   inliers [B][m] uint8 at the positions of keypoints0; num_inliers [B]; best_model [B] = hypothesis * 3 + solution of the RANSAC
+ *   winner.  With fewer than 7 valid matches or no model: F = 0, no inliers, best_model = -1.  workspace:
+ *   og_fundamental_matrix_workspace_bytes, 16-byte aligned.  OG_E_INVALID for hypotheses <= 0, 3 batch hypotheses > 2^30 (the
+ *   workspace size is then 0), refine < 0 or a negative threshold.  Four kernels, no host synchronisation, bit-identical from run to run. */
+int og_fundamental_7pt(int32_t count, const double* x0, const double* x1, double* F, int32_t* num_solutions, void* stream);
+size_t og_fundamental_matrix_workspace_bytes(int32_t batch, int32_t m, int32_t hypotheses);
+int og_fundamental_matrix(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                          const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
+                          int32_t refine, uint64_t seed, int64_t pair_offset, double* F, uint8_t* inliers,
+                          int32_t* num_inliers, int32_t* best_model, void* workspace_dev, void* stream);
+
 /* ABI v13 -- the SuperPoint detector / descriptor (models/features/superpoint/model.py, SuperPointNet / SuperPointNetBn), inference
  * only (eval-mode BatchNorm, folded at pack time).  descriptor_dim 256.  Image [B][H][W] fp32, H, W >= 8, B * H * W <= 2^26;
  * Hc = H / 8, Wc = W / 8 (floor, as the three 2x2 max-pools), the heatmap is [B][8 Hc][8 Wc].

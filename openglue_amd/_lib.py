@@ -165,6 +165,10 @@ SYMBOLS = {
     "og_relative_pose_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "og_relative_pose": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i32, C.c_uint64, _i64,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_fundamental_7pt": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _vp]),
+    "og_fundamental_matrix_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "og_fundamental_matrix": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f, _i32, _i32, C.c_uint64, _i64,
+                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_superpoint_packed_bytes": (_sz, [_i32]),
     "og_superpoint_pack": (C.c_int, [_i32, _i32, _f, _vp, _vp]),
     "og_superpoint_capacity": (C.c_int, [_i32, _i32, _i32]),

@@ -26,6 +26,7 @@
 //                         checks spread over lanes, errors against the ground truth
 //    Every launch count is fixed: 5 kernels whatever the batch.
 #include "og_common.h"
+#include "og_ransac.h"      // finite, pmul, peval, mix64, draw_distinct, block_sum_int, jacobi3
 
 namespace {
 
@@ -76,25 +77,6 @@ __host__ __device__ inline void cmul_acc(const Quad& q, const Lin& l, double s, 
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 out[mono(ex(i) + ex(j) + ex(k), ey(i) + ey(j) + ey(k), ez(i) + ez(j) + ez(k))] += s * q.c[qidx(i, j)] * l.c[k];
-}
-
-__host__ __device__ inline bool finite(double v) { return v - v == 0.0; }
-
-template <int NA, int NB>
-__host__ __device__ inline void pmul(const double (&a)[NA], const double (&b)[NB], double (&o)[NA + NB - 1]) {
-#pragma unroll
-    for (int i = 0; i < NA + NB - 1; ++i) o[i] = 0.0;
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) o[i + j] += a[i] * b[j];
-}
-template <int N>
-__host__ __device__ inline double peval(const double* p, double t) {       // ascending coefficients, N of them
-    double v = p[N - 1];
-#pragma unroll
-    for (int i = N - 2; i >= 0; --i) v = v * t + p[i];
-    return v;
 }
 
 // Stage 1 of the solver for one problem.  x0, x1: 5 calibrated points each ([5][2]).  A: the 10 x 20 elimination matrix,
@@ -471,13 +453,6 @@ __host__ __device__ inline int essential_roots(const double* inter, int IS, doub
 }
 
 // ------------------------------------------------------------------------------------------------ sampling
-__host__ __device__ inline uint64_t mix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 struct PoseWs {
     double4* pts;          // [B][m] calibrated (u0, v0, u1, v1) of every keypoint with a valid match
     int* idx;              // [B][m] the valid keypoints in index order
@@ -532,20 +507,11 @@ __global__ void __launch_bounds__(kPolyLds) solve_poly_kernel(SolveSrc src, int 
         const int b = p / src.H, h = p - b * src.H;
         const int n = src.cnt[b];
         if (n < 5) { inter[75] = 0.0; return; }
-        const uint64_t base = mix64(mix64(src.seed) ^ (uint64_t)(src.pair_offset + b)) ^ ((uint64_t)h << 8);
         int pick[5];
+        draw_distinct<5>(src.seed, (uint64_t)(src.pair_offset + b), h, n, pick);
 #pragma unroll
         for (int j = 0; j < 5; ++j) {
-            int r = (int)(((mix64(base + j) >> 32) * (uint64_t)n) >> 32);
-            // distinct: step to the next unused position (terminates: n >= 5 > j)
-#pragma unroll
-            for (int t = 0; t < 5; ++t) {
-                bool dup = false;
-#pragma unroll
-                for (int q = 0; q < j; ++q) dup = dup || pick[q] == r;
-                r = dup ? (r + 1 == n ? 0 : r + 1) : r;
-            }
-            pick[j] = r;
+            const int r = pick[j];
             const double4 q = src.pts[(int64_t)b * src.m + src.idx[(int64_t)b * src.m + r]];
             x0[2 * j] = q.x; x0[2 * j + 1] = q.y; x1[2 * j] = q.z; x1[2 * j + 1] = q.w;
         }
@@ -567,13 +533,6 @@ struct Geo {
     int B, m, n;
 };
 
-__device__ inline bool valid_match(const Geo& g, int b, int i, int& j) {
-    const int lim = g.nk0 ? min(g.nk0[b], g.m) : g.m;
-    const int64_t v = g.matches0[(int64_t)b * g.m + i];
-    j = (int)v;
-    return i < lim && v >= 0 && v < g.n;
-}
-
 // calibrated (x - c) / f in fp64, utils/misc.py:5-7
 __device__ inline double4 calibrate(const Geo& g, int b, int i, int j) {
     const float* K0 = g.K0 + b * 9; const float* K1 = g.K1 + b * 9;
@@ -581,18 +540,6 @@ __device__ inline double4 calibrate(const Geo& g, int b, int i, int j) {
     const float2 c = ((const float2*)g.k1)[(int64_t)b * g.n + j];
     return make_double4(((double)a.x - K0[2]) / K0[0], ((double)a.y - K0[5]) / K0[4],
                         ((double)c.x - K1[2]) / K1[0], ((double)c.y - K1[5]) / K1[4]);
-}
-
-__device__ inline int block_sum_int(int v, int* red) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    int t = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-    return t;
 }
 
 __global__ void __launch_bounds__(256) precision_kernel(Geo g, double threshold, float* precision, float* matching_score, int* num_correct) {
@@ -633,23 +580,9 @@ __global__ void __launch_bounds__(256) precision_kernel(Geo g, double threshold,
 // ------------------------------------------------------------------------------------------------ relative pose
 __global__ void __launch_bounds__(256) prep_kernel(Geo g, float ransac_threshold, PoseWs w) {
     __shared__ int wsum[4];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int base = 0;
-    for (int i0 = 0; i0 < g.m; i0 += 256) {
-        const int i = i0 + threadIdx.x;
-        int j = 0;
-        const bool v = i < g.m && valid_match(g, b, i, j);
-        if (v) w.pts[(int64_t)b * g.m + i] = calibrate(g, b, i, j);
-        const unsigned long long bal = __ballot(v);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int q = 0; q < wid; ++q) off += wsum[q];
-        if (v) w.idx[(int64_t)b * g.m + off + before] = i;
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
-        __syncthreads();
-    }
+    const int b = blockIdx.x;
+    const int base = compact_valid_matches(g, b, w.idx + (int64_t)b * g.m, wsum,
+                                           [&](int i, int j) { w.pts[(int64_t)b * g.m + i] = calibrate(g, b, i, j); });
     if (threadIdx.x == 0) {
         const float* K0 = g.K0 + b * 9; const float* K1 = g.K1 + b * 9;
         // utils/metrics.py:90 in fp32: 2 thr / mean(K0[0,0] + K1[0,0], K0[1,1] + K1[1,1])
@@ -705,44 +638,6 @@ __global__ void __launch_bounds__(256) score_kernel(PoseWs w, int m, int H) {
         key = other > key ? other : key;
     }
     if ((threadIdx.x & 63) == 0 && key) atomicMax(&w.best[b], key);
-}
-
-// symmetric 3 x 3 eigen-decomposition by cyclic Jacobi: A = V diag(A) V^T on return
-__device__ inline void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 12; ++sweep) {
-#pragma unroll
-        for (int pq = 0; pq < 3; ++pq) {
-            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-            const double apq = A[p][q];
-            if (fabs(apq) < 1e-300) continue;
-            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-            // A <- J^T A J, V <- V J with J_pp = J_qq = c, J_pq = s, J_qp = -s
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double akp = A[k][p], akq = A[k][q];
-                A[k][p] = c * akp - s * akq;
-                A[k][q] = s * akp + c * akq;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double apk = A[p][k], aqk = A[q][k];
-                A[p][k] = c * apk - s * aqk;
-                A[q][k] = s * apk + c * aqk;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double vkp = V[k][p], vkq = V[k][q];
-                V[k][p] = c * vkp - s * vkq;
-                V[k][q] = s * vkp + c * vkq;
-            }
-        }
-    }
 }
 
 __device__ inline double det3(const double (&M)[3][3]) {

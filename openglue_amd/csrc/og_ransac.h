@@ -1,0 +1,139 @@
+// Helpers the two RANSAC units share (metrics.hip: five-point / essential matrix, geometry.hip: seven-point / fundamental matrix).
+// Internal, not part of the ABI.  Everything lives in the unnamed namespace of the including unit, as it did in metrics.hip.
+#pragma once
+#include "og_common.h"
+
+namespace {
+
+__host__ __device__ inline bool finite(double v) { return v - v == 0.0; }
+
+template <int NA, int NB>
+__host__ __device__ inline void pmul(const double (&a)[NA], const double (&b)[NB], double (&o)[NA + NB - 1]) {
+#pragma unroll
+    for (int i = 0; i < NA + NB - 1; ++i) o[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < NA; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) o[i + j] += a[i] * b[j];
+}
+template <int N>
+__host__ __device__ inline double peval(const double* p, double t) {       // ascending coefficients, N of them
+    double v = p[N - 1];
+#pragma unroll
+    for (int i = N - 2; i >= 0; --i) v = v * t + p[i];
+    return v;
+}
+
+// counter-based hash (splitmix64 finaliser): the RANSAC draws
+__host__ __device__ inline uint64_t mix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// K distinct positions in [0, n), n >= K, for hypothesis h of pair `pair`: draw j is the hash of (seed, pair, h, j) scaled to n, then
+// stepped to the next unused position (at most j steps)
+template <int K>
+__host__ __device__ inline void draw_distinct(uint64_t seed, uint64_t pair, int h, int n, int (&pick)[K]) {
+    const uint64_t base = mix64(mix64(seed) ^ pair) ^ ((uint64_t)h << 8);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        int r = (int)(((mix64(base + j) >> 32) * (uint64_t)n) >> 32);
+#pragma unroll
+        for (int t = 0; t < K; ++t) {
+            bool dup = false;
+#pragma unroll
+            for (int q = 0; q < j; ++q) dup = dup || pick[q] == r;
+            r = dup ? (r + 1 == n ? 0 : r + 1) : r;
+        }
+        pick[j] = r;
+    }
+}
+
+__device__ inline int block_sum_int(int v, int* red) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if (lane == 0) red[wid] = v;
+    __syncthreads();
+    int t = 0;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+    return t;
+}
+
+// The validity rule of both units: keypoint i of pair b is matched when i < num_keypoints0[b] and 0 <= matches0[i] < n.  G carries
+// matches0 [B][m] int64, nk0 [B] (or null: m), m and n.
+template <class G>
+__device__ inline bool valid_match(const G& g, int b, int i, int& j) {
+    const int lim = g.nk0 ? min(g.nk0[b], g.m) : g.m;
+    const int64_t v = g.matches0[(int64_t)b * g.m + i];
+    j = (int)v;
+    return i < lim && v >= 0 && v < g.n;
+}
+
+// One workgroup of 256 compacts the valid matches of pair b in index order into idx (the pair's row, m entries) and returns their
+// number in every thread.  each(i, j) runs for every valid match in the thread that found it.  wsum: 4 ints of LDS.  The last
+// barrier orders the writes to idx before whatever the workgroup reads from it afterwards.
+template <class G, class Each>
+__device__ inline int compact_valid_matches(const G& g, int b, int* idx, int* wsum, Each each) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < g.m; i0 += 256) {
+        const int i = i0 + threadIdx.x;
+        int j = 0;
+        const bool v = i < g.m && valid_match(g, b, i, j);
+        if (v) each(i, j);
+        const unsigned long long bal = __ballot(v);
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wid] = __popcll(bal);
+        __syncthreads();
+        int off = base;
+        for (int q = 0; q < wid; ++q) off += wsum[q];
+        if (v) idx[off + before] = i;
+        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        __syncthreads();
+    }
+    return base;
+}
+
+// symmetric 3 x 3 eigen-decomposition by cyclic Jacobi: A = V diag(A) V^T on return
+__device__ inline void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) V[i][j] = i == j ? 1.0 : 0.0;
+    for (int sweep = 0; sweep < 12; ++sweep) {
+#pragma unroll
+        for (int pq = 0; pq < 3; ++pq) {
+            const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+            const double apq = A[p][q];
+            if (fabs(apq) < 1e-300) continue;
+            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+            // A <- J^T A J, V <- V J with J_pp = J_qq = c, J_pq = s, J_qp = -s
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double akp = A[k][p], akq = A[k][q];
+                A[k][p] = c * akp - s * akq;
+                A[k][q] = s * akp + c * akq;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double apk = A[p][k], aqk = A[q][k];
+                A[p][k] = c * apk - s * aqk;
+                A[q][k] = s * apk + c * aqk;
+            }
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const double vkp = V[k][p], vkq = V[k][q];
+                V[k][p] = c * vkp - s * vkq;
+                V[k][q] = s * vkp + c * vkq;
+            }
+        }
+    }
+}
+
+}  // namespace

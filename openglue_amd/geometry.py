@@ -1,0 +1,102 @@
+"""Uncalibrated geometric verification on HIP kernels: the last step of the reference's inference.py, which takes the matches to
+cv2.findFundamentalMat(keypoints0, keypoints1, cv2.USAC_MAGSAC, 1.0, 0.999, 100000) and keeps the inliers (inference.py:214-235).
+
+  fundamental_matrix   a whole SuperGlue.match batch (matches0 with -1 holes, ragged num_keypoints0) -> F, inlier mask, counts
+  find_fundamental     one pair of compacted matches -> (F, inliers), cv2's return order
+  fundamental_7pt      the seven-point minimal solver on its own
+
+Thin wrappers over og_fundamental_matrix / og_fundamental_7pt (include/openglue_amd.h, csrc/geometry.hip); GPU tensors only, no
+host synchronisation.  Per pair: Hartley normalisation of the valid matches, `hypotheses` seven-point samples drawn by a
+counter-based hash of (seed, pair_offset + pair, hypothesis), every model (up to 3 per sample) scored by its number of matches with
+squared Sampson error <= threshold^2 (pixels), the winner by most inliers and lowest (hypothesis, solution) on ties, then `refine`
+normalised eight-point refits on the inliers, each kept if it loses no inlier.  Outputs are bit-identical from run to run, and B
+calls of one pair with pair_offset = b give what one batched call gives.
+
+Where this deliberately differs from cv2.USAC_MAGSAC:
+  * no sigma-consensus scoring: `threshold` is a plain inlier threshold on the Sampson error;
+  * the sample count is fixed: every one of `hypotheses` samples is evaluated, there is no adaptive stop (2048 gives 0.999
+    confidence down to an inlier ratio of about 0.45: ln 0.001 / ln(1 - 0.45^7) ~ 1850);
+  * the random draws are the hash's, not OpenCV's generator;
+  * there is no degeneracy test for planar scenes or dominant planes: for such input F is whatever the data support (a homography
+    leaves a family of F that fit equally well), and the mask is still finite and deterministic.
+With fewer than 7 valid matches, or no surviving model, F is zero, no match is an inlier and best_model is -1 (cv2 returns None).
+"""
+from __future__ import annotations
+
+from typing import Dict, Tuple
+
+import torch
+
+from . import _lib
+
+
+def _shape(t, name: str) -> Tuple[int, ...]:
+    """The shape of a tensor argument; anything else gets gpu_tensor's refusal.  Shapes and scalar arguments are checked before the
+    device, so a bad call fails the same way wherever its tensors live."""
+    if not isinstance(t, torch.Tensor):
+        _lib.gpu_tensor(t, name)
+    return tuple(t.shape)
+
+
+def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold: float = 1.0, hypotheses: int = 2048,
+                       refine: int = 2, seed: int = 0, pair_offset: int = 0) -> Dict[str, torch.Tensor]:
+    """keypoints0 [B, M, 2], keypoints1 [B, N, 2] (pixels), matches0 [B, M] (-1 or outside [0, N): no match), num_keypoints0 [B]
+    (None: M) -> {'F' [B, 3, 3] float64 in pixels with x1^T F x0 = 0, unit Frobenius norm, largest entry positive; 'inliers' [B, M]
+    bool at the positions of keypoints0; 'num_inliers' [B] int32; 'best_model' [B] int32 = hypothesis * 3 + solution of the RANSAC
+    winner, -1 without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is)."""
+    s0, s1, sm = _shape(keypoints0, "keypoints0"), _shape(keypoints1, "keypoints1"), _shape(matches0, "matches0")
+    if len(s0) != 3 or s0[2] != 2 or len(s1) != 3 or s1[2] != 2 or s1[0] != s0[0] or s0[0] == 0:
+        raise ValueError(f"keypoints0 / keypoints1 must be [B, M, 2] / [B, N, 2] with B > 0, got {list(s0)} / {list(s1)}")
+    B, M, N = s0[0], s0[1], s1[1]
+    if sm != (B, M):
+        raise ValueError(f"matches0 must be [B, M] = [{B}, {M}], got {list(sm)}")
+    if num_keypoints0 is not None and _shape(num_keypoints0, "num_keypoints0") != (B,):
+        raise ValueError(f"num_keypoints0 must be [B] = [{B}], got {list(num_keypoints0.shape)}")
+    hypotheses, refine = int(hypotheses), int(refine)
+    if hypotheses <= 0 or refine < 0 or not float(threshold) >= 0.0:
+        raise ValueError(f"hypotheses must be positive, refine and threshold non-negative, got {hypotheses}, {refine}, {threshold}")
+    if 3 * B * hypotheses > 2 ** 30:
+        raise ValueError(f"3 * batch * hypotheses must not exceed 2^30, got 3 * {B} * {hypotheses}")
+    k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
+    k1 = _lib.gpu_tensor(keypoints1, "keypoints1", convert=True)
+    m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
+    nk = None if num_keypoints0 is None else _lib.gpu_tensor(num_keypoints0, "num_keypoints0", torch.int32, convert=True)
+    dev = k0.device
+    ws, wp = _lib.workspace(_lib.load().og_fundamental_matrix_workspace_bytes(B, M, hypotheses), dev)      # sizes checked above
+    F = torch.empty(B, 3, 3, device=dev, dtype=torch.float64)
+    inl = torch.empty(B, max(M, 1), device=dev, dtype=torch.uint8)
+    ninl = torch.empty(B, device=dev, dtype=torch.int32)
+    best = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.call("og_fundamental_matrix", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
+              hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), F.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
+              best.data_ptr(), wp, _lib.STREAM)
+    return {"F": F, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best}
+
+
+def find_fundamental(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One pair as inference.py passes it to cv2.findFundamentalMat: matched keypoints [K, 2] of both images -> (F [3, 3] float64,
+    inliers [K] bool).  Keyword arguments as fundamental_matrix (threshold, hypotheses, refine, seed, pair_offset)."""
+    s0, s1 = _shape(matched_kpts0, "matched_kpts0"), _shape(matched_kpts1, "matched_kpts1")
+    if len(s0) != 2 or s0[1] != 2 or s1 != s0:
+        raise ValueError(f"matched_kpts0 / matched_kpts1 must both be [K, 2], got {list(s0)} / {list(s1)}")
+    k0 = _lib.gpu_tensor(matched_kpts0, "matched_kpts0", convert=True)
+    k1 = _lib.gpu_tensor(matched_kpts1, "matched_kpts1", convert=True)
+    m0 = torch.arange(k0.shape[0], device=k0.device).unsqueeze(0)
+    r = fundamental_matrix(k0.unsqueeze(0), k1.unsqueeze(0), m0, **kw)
+    return r["F"][0], r["inliers"][0]
+
+
+def fundamental_7pt(x0: torch.Tensor, x1: torch.Tensor):
+    """The seven-point minimal solver on its own: x0, x1 [count, 7, 2] correspondences (x1^T F x0 = 0) with coordinates of order 1
+    -> (F [count, 3, 3, 3] float64, unit Frobenius norm, zero past num_solutions; num_solutions [count] int32, 0..3)."""
+    s0, s1 = _shape(x0, "x0"), _shape(x1, "x1")
+    if len(s0) != 3 or s0[1:] != (7, 2) or s1 != s0 or not 0 < s0[0] <= 2 ** 30:
+        raise ValueError(f"x0 / x1 must both be [count, 7, 2] with 0 < count <= 2^30, got {list(s0)} / {list(s1)}")
+    a = _lib.gpu_tensor(x0, "x0", torch.float64, convert=True)
+    b = _lib.gpu_tensor(x1, "x1", torch.float64, convert=True)
+    count = a.shape[0]
+    dev = a.device
+    F = torch.empty(count, 3, 3, 3, device=dev, dtype=torch.float64)
+    ns = torch.empty(count, device=dev, dtype=torch.int32)
+    _lib.call("og_fundamental_7pt", dev, count, a.data_ptr(), b.data_ptr(), F.data_ptr(), ns.data_ptr(), _lib.STREAM)
+    return F, ns
