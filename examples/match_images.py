@@ -1,9 +1,11 @@
-"""Two images to verified matches on the GPU: SuperPointNetBn -> OpenGlueMatcher(SuperGlue) -> find_fundamental, the whole of the
-reference's inference.py run_inference, on a synthetic homography pair with seeded weights.  Prints the shapes and the time per stage.
+"""Two images to verified matches on the GPU: SuperPointNetBn (or SIFT) -> OpenGlueMatcher(SuperGlue) -> find_fundamental, the whole
+of the reference's inference.py run_inference, on a synthetic homography pair with seeded weights.  Prints the shapes and the time per stage.
 The pair is related by a homography, which is degenerate for a fundamental matrix (a family of F fits it equally well): the inlier
 count is shown, the accuracy of the stage is the business of tests/test_gpu_geometry.py.
 
-    python examples/match_images.py [--size 480x640] [--keypoints 2048] [--match-threshold 0.2]
+    python examples/match_images.py [--size 480x640] [--keypoints 2048] [--match-threshold 0.2] [--features {superpoint,sift}]
+
+--features sift runs the reference's 128-d pipeline: the SIFT extractor (openglue_amd/sift.py) and a 128-d SuperGlue.
 
 The seeded weights are not trained: at the reference's threshold of 0.2 they may leave no match at all, and the last stage then
 times its four launches on an empty pair.  --match-threshold 0 keeps every mutual best match and gives the stage real work.
@@ -19,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from examples.openglue_matcher import OpenGlueMatcher  # noqa: E402
 from openglue_amd import synthetic as syn  # noqa: E402
 from openglue_amd.geometry import find_fundamental  # noqa: E402
+from openglue_amd.sift import SIFT  # noqa: E402
 from openglue_amd.superglue import SuperGlue  # noqa: E402
 from openglue_amd.superpoint import SuperPointNetBn  # noqa: E402
 
@@ -28,15 +31,19 @@ def main():
     ap.add_argument("--size", default="480x640")
     ap.add_argument("--keypoints", type=int, default=2048)
     ap.add_argument("--match-threshold", type=float, default=0.2)
+    ap.add_argument("--features", choices=("superpoint", "sift"), default="superpoint")
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split("x"))
     dev = torch.device("cuda:0")
     img0 = syn.make_image(H, W, seed=1)
     img1 = syn.warp_image(img0, syn.random_homography(H, W, seed=2))
-    sp = SuperPointNetBn(max_keypoints=a.keypoints, keypoint_threshold=0.005)
-    sp.load_state_dict(syn.make_superpoint_state_dict(True, seed=1))
-    sp = sp.eval().to(dev)
-    cfg = syn.make_config(descriptor_dim=256, num_stages=9, num_heads=4, num_iters=20, side_info_size=1)
+    if a.features == "sift":
+        sp = SIFT(max_keypoints=a.keypoints).to(dev)
+    else:
+        sp = SuperPointNetBn(max_keypoints=a.keypoints, keypoint_threshold=0.005)
+        sp.load_state_dict(syn.make_superpoint_state_dict(True, seed=1))
+        sp = sp.eval().to(dev)
+    cfg = syn.make_config(descriptor_dim=128 if a.features == "sift" else 256, num_stages=9, num_heads=4, num_iters=20, side_info_size=1)
     sg = SuperGlue(cfg).eval()
     sg.load_state_dict(syn.make_state_dict(cfg, seed=0))
     sg = sg.to(dev)
@@ -57,7 +64,7 @@ def main():
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     print(f"{H}x{W}: {lafs.shape[1]} keypoints per image, {out['keypoints0'].shape[0]} matches")
-    print(f"SuperPoint on both images {1e3 * (t1 - t0):.2f} ms; images -> matches {1e3 * (t2 - t1):.2f} ms")
+    print(f"{'SIFT' if a.features == 'sift' else 'SuperPoint'} on both images {1e3 * (t1 - t0):.2f} ms; images -> matches {1e3 * (t2 - t1):.2f} ms")
     print(f"fundamental matrix: {int(inliers.sum())} inliers of {inliers.shape[0]} matches, {1e3 * (t3 - t2):.2f} ms")
 
 

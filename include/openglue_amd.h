@@ -660,6 +660,53 @@ int og_adam_step(int32_t count, const void* const* params, const void* table_dev
                  int64_t total, float* grad, float* exp_avg, float* exp_avg_sq, double* workspace_dev, double lr, double gamma,
                  double beta1, double beta2, double eps, int32_t clip, double max_norm, void* stream);
 
+/* ABI v14, additive -- the SIFT keypoint extractor (csrc/sift.hip): DoG detector and SIFT / RootSIFT descriptor, a drop-in for the
+ * reference's OPENCV_SIFT features (models/features/opencv/): Lowe 2004 with OpenCV's constants (3 layers per octave, sigma 1.6, first
+ * octave -1, assumed input blur 0.5), the contrast and edge tests off as the reference sets them, then the reference's own radius NMS,
+ * top-k, LAFs and descriptor normalisation (base.py).  Not bit-identical to cv2.SIFT_create; tests/sift_ref.py is the specification.
+ * Limits: 8 <= H, W <= 8192 and B * H * W <= 2^22; anything else (a null pointer included) returns OG_E_INVALID, og_sift_workspace_bytes 0.
+ *
+ * Geometry (og_sift_geometry, host arithmetic): out[0] = octaves built, out[1] = cap, the keypoint capacity per image (max(1024,
+ *   H W / 2)), out[2] = cap2 = cap + cap / 4, the capacity after one keypoint per orientation; out[3 + 2 o], out[4 + 2 o] = h, w of
+ *   octave o (2H x 2W, halved with floor; octaves with a side below 11 are not built); 35 ints.  Per image, gauss is
+ *   [octave][6][h][w] and dog [octave][5][h][w], octaves packed one after the other.  The select stage holds 32 cap2 neighbour entries.
+ * counts, int32 [4 B + 1], is filled along the way: [b] keypoints detected, [B + b] oriented keypoints, [2 B + b] kept after NMS and
+ *   top-k, [3 B + b] neighbour-list entries, [4 B] = min_b counts[2 B + b], the rows every image puts out (min_stack).  A count above
+ *   its capacity means the buffers were too small for this image: the stages stay in bounds and process the first cap / cap2, the
+ *   caller must treat it as an error (openglue_amd/sift.py raises).
+ * All stages of one call share one workspace (og_sift_workspace_bytes, 16-byte aligned) and run in order on one stream.
+ *
+ * og_sift_pyramid: image [B][H][W] in [0, 1] -> u = clamp(trunc(255.f x), 0, 255), bilinear 2x (pixel-centre aligned), blur
+ *   sqrt(1.6^2 - 1), then per octave 6 incrementally blurred images (radius (round(8 s + 1) | 1) / 2, fp64-normalised fp32 taps,
+ *   reflect-101, rows then columns, fp32) and their 5 differences; the next octave starts from every second pixel of image 3.
+ * og_sift_detect: extrema of DoG layers 1..3 inside a 5-pixel border (> 0 and >= all 26 neighbours, or < 0 and <= all), refined in
+ *   fp64 by up to 5 Newton steps.  det_i [B][cap][4] = octave, layer, row, column of the converged sample; det_f [B][cap][4] (double) =
+ *   x, y in input pixels ((c + x_c) 2^(o-1) - 0.25), size = 2 * 1.6 * 2^((l + x_l) / 3) * 2^(o-1), response |D + grad . x / 2| / 255.
+ *   Order: octave, layer, row, column of the extremum each started from.
+ * og_sift_orient: 36-bin gradient histogram (radius round(4.5 s), weight std 1.5 s, [1 4 6 4 1] / 16 smoothing), one keypoint per
+ *   local peak >= 0.8 max by descending height, parabolic interpolation; upright != 0: angle 0.  ori_i [B][cap2][6] = octave, layer,
+ *   row, column, orientation rank, source keypoint; ori_f [B][cap2][5] (float) = x, y, size, angle in degrees [0, 360), response.
+ * og_sift_describe: desc [B][cap2][128], [row bin][column bin][orientation bin]: bin width 3 s, Gaussian window of 2 bins, trilinear;
+ *   L2-normalise, clip 0.2, renormalise, quantize != 0: min(255, round(512 v)); then rootsift > 0: L1-normalise and square root,
+ *   0: L2-normalise, < 0: left as it is (the bytes).  An all-zero descriptor stays zero.
+ * og_sift_select: greedy radius NMS in descending response (radius nms_diameter / 2, distance <= radius; <= 0: none), then the
+ *   max_kpts strongest (<= 0: all).  sel [B][cap2] = indices into ori_* in output order: descending response, equal ones by (octave,
+ *   layer, row, column, orientation rank), then index.  Equal to the sequential greedy pass.
+ * og_sift_gather: n = counts[4 B] -> lafs [B][n][2][3] (scale 6 size, angle deg2rad(-angle)), scores [B][n], descriptors [B][n][128]. */
+int og_sift_geometry(int32_t H, int32_t W, int32_t* out);
+size_t og_sift_workspace_bytes(int32_t batch, int32_t H, int32_t W);
+int og_sift_pyramid(int32_t batch, int32_t H, int32_t W, const float* image, float* gauss, float* dog, void* workspace_dev, void* stream);
+int og_sift_detect(int32_t batch, int32_t H, int32_t W, const float* dog, int32_t* det_i, double* det_f, int32_t* counts,
+                   void* workspace_dev, void* stream);
+int og_sift_orient(int32_t batch, int32_t H, int32_t W, int32_t upright, const float* gauss, const int32_t* det_i, const double* det_f,
+                   int32_t* counts, int32_t* ori_i, float* ori_f, void* workspace_dev, void* stream);
+int og_sift_describe(int32_t batch, int32_t H, int32_t W, int32_t quantize, int32_t rootsift, const float* gauss, const int32_t* ori_i,
+                     const float* ori_f, const int32_t* counts, float* desc, void* stream);
+int og_sift_select(int32_t batch, int32_t H, int32_t W, float nms_diameter, int32_t max_kpts, const int32_t* ori_i, const float* ori_f,
+                   int32_t* counts, int32_t* sel, void* workspace_dev, void* stream);
+int og_sift_gather(int32_t batch, int32_t H, int32_t W, int32_t n, const int32_t* sel, const float* ori_f, const float* desc,
+                   float* lafs, float* scores, float* descriptors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
