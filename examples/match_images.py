@@ -3,9 +3,11 @@ of the reference's inference.py run_inference, on a synthetic homography pair wi
 The pair is related by a homography, which is degenerate for a fundamental matrix (a family of F fits it equally well): the inlier
 count is shown, the accuracy of the stage is the business of tests/test_gpu_geometry.py.
 
-    python examples/match_images.py [--size 480x640] [--keypoints 2048] [--match-threshold 0.2] [--features {superpoint,sift}]
+    python examples/match_images.py [--size 480x640] [--keypoints 2048] [--match-threshold 0.2] [--features {superpoint,sift,dog_affnet_hardnet}]
 
 --features sift runs the reference's 128-d pipeline: the SIFT extractor (openglue_amd/sift.py) and a 128-d SuperGlue.
+--features dog_affnet_hardnet runs DoG + AffNet + OriNet + HardNet (openglue_amd/affnet_hardnet.py, seeded weights) with the affine
+LAF side information: laf_to_sideinfo_method "affine", side_info_size 6.
 
 The seeded weights are not trained: at the reference's threshold of 0.2 they may leave no match at all, and the last stage then
 times its four launches on an empty pair.  --match-threshold 0 keeps every mutual best match and gives the stage real work.
@@ -20,6 +22,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from examples.openglue_matcher import OpenGlueMatcher  # noqa: E402
 from openglue_amd import synthetic as syn  # noqa: E402
+from openglue_amd.affnet_hardnet import DoGAffNetHardNet  # noqa: E402
 from openglue_amd.geometry import find_fundamental  # noqa: E402
 from openglue_amd.sift import SIFT  # noqa: E402
 from openglue_amd.superglue import SuperGlue  # noqa: E402
@@ -31,23 +34,31 @@ def main():
     ap.add_argument("--size", default="480x640")
     ap.add_argument("--keypoints", type=int, default=2048)
     ap.add_argument("--match-threshold", type=float, default=0.2)
-    ap.add_argument("--features", choices=("superpoint", "sift"), default="superpoint")
+    ap.add_argument("--features", choices=("superpoint", "sift", "dog_affnet_hardnet"), default="superpoint")
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split("x"))
     dev = torch.device("cuda:0")
     img0 = syn.make_image(H, W, seed=1)
     img1 = syn.warp_image(img0, syn.random_homography(H, W, seed=2))
+    affine = a.features == "dog_affnet_hardnet"
     if a.features == "sift":
         sp = SIFT(max_keypoints=a.keypoints).to(dev)
+    elif affine:
+        sp = DoGAffNetHardNet(max_keypoints=a.keypoints)
+        sp.hardnet.load_state_dict(syn.make_patchnet_state_dict("hardnet", seed=1))
+        sp.affnet.load_state_dict(syn.make_patchnet_state_dict("affnet", seed=1))
+        sp.orinet.angle_detector.load_state_dict(syn.make_patchnet_state_dict("orinet", seed=1))
+        sp = sp.eval().to(dev)
     else:
         sp = SuperPointNetBn(max_keypoints=a.keypoints, keypoint_threshold=0.005)
         sp.load_state_dict(syn.make_superpoint_state_dict(True, seed=1))
         sp = sp.eval().to(dev)
-    cfg = syn.make_config(descriptor_dim=128 if a.features == "sift" else 256, num_stages=9, num_heads=4, num_iters=20, side_info_size=1)
+    cfg = syn.make_config(descriptor_dim=256 if a.features == "superpoint" else 128, num_stages=9, num_heads=4, num_iters=20,
+                          side_info_size=6 if affine else 1)
     sg = SuperGlue(cfg).eval()
     sg.load_state_dict(syn.make_state_dict(cfg, seed=0))
     sg = sg.to(dev)
-    matcher = OpenGlueMatcher(sp, sg, {"superglue": {"laf_to_sideinfo_method": "none"}, "inference": {"match_threshold": a.match_threshold}})
+    matcher = OpenGlueMatcher(sp, sg, {"superglue": {"laf_to_sideinfo_method": "affine" if affine else "none"}, "inference": {"match_threshold": a.match_threshold}})
     data = {"image0": img0.to(dev), "image1": img1.to(dev)}
     for _ in range(2):                      # warm-up: packing, allocator
         out = matcher(data)
@@ -64,7 +75,7 @@ def main():
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     print(f"{H}x{W}: {lafs.shape[1]} keypoints per image, {out['keypoints0'].shape[0]} matches")
-    print(f"{'SIFT' if a.features == 'sift' else 'SuperPoint'} on both images {1e3 * (t1 - t0):.2f} ms; images -> matches {1e3 * (t2 - t1):.2f} ms")
+    print(f"{ {'sift': 'SIFT', 'superpoint': 'SuperPoint', 'dog_affnet_hardnet': 'DoG + AffNet + OriNet + HardNet'}[a.features]} on both images {1e3 * (t1 - t0):.2f} ms; images -> matches {1e3 * (t2 - t1):.2f} ms")
     print(f"fundamental matrix: {int(inliers.sum())} inliers of {inliers.shape[0]} matches, {1e3 * (t3 - t2):.2f} ms")
 
 

@@ -707,6 +707,38 @@ int og_sift_select(int32_t batch, int32_t H, int32_t W, float nms_diameter, int3
 int og_sift_gather(int32_t batch, int32_t H, int32_t W, int32_t n, const int32_t* sel, const float* ori_f, const float* desc,
                    float* lafs, float* scores, float* descriptors, void* stream);
 
+/* ABI v14, additive -- the patch networks behind the DoG detector (csrc/patchnet.hip): the reference's OPENCVDoGAffNetHardNet
+ * (models/features/opencv/dog_affnet_harnet.py) after its detector: lafs = orinet(affnet(lafs, image), image), 32 x 32 patches from an
+ * image pyramid, HardNet descriptors.  A kornia 0.6-era reading, pinned by tests/patchnet_ref.py; exact fp32, deterministic.
+ * kind: 0 HardNet (1-32-32-64-64-128-128, 128 outputs), 1 AffNet (1-16-16-32-32-64-64, 3 outputs), 2 OriNet (as AffNet, 2 outputs).
+ * Limits: 1 <= H, W <= 8192 and B * H * W <= 2^22, n <= 2^24; anything else (a null pointer included) returns OG_E_INVALID.
+ *
+ * og_patch_geometry (host): out[0] = pyramid levels (built while min(h, w) >= 32, at most 12), out[1] = floats per image, out[2 + 2 l],
+ *   out[3 + 2 l] = h, w of level l (halved with floor); 26 ints.  The pyramid buffer is [level][B][h][w], levels one after the other.
+ * og_patch_workspace_bytes: one scratch for og_patch_pyramid on [batch][H][W] and og_patchnet_forward on n patches (either part may
+ *   be all zeros); 16-byte aligned.  0: unsupported.
+ * og_patch_pyramid: level l + 1 = level l blurred with [1 4 6 4 1] x [1 4 6 4 1] / 256 (reflect border, no edge repeat), resized
+ *   bilinearly (align_corners false) to half size.
+ * og_patch_extract: lafs [B][n][2][3] -> patches [B n][32][32].  Level max(0, floor(log2(2 scale / 32))), scale = sqrt |det A|; a level
+ *   that was not built gives a zero patch; bilinear, border clamp.  upright != 0: A is replaced by scale * I.  normalize != 0:
+ *   (x - mean) / (std + 1e-6) per patch, unbiased std.
+ * og_patchnet_pack (host): params = host pointers: weight, BatchNorm running_mean, running_var of features.0 / 3 / 6 / 9 / 12 / 15 (18),
+ *   features.19.weight, then HardNet: features.20 running_mean, running_var; AffNet / OriNet: features.19.bias.  BatchNorm (affine
+ *   false) is folded into its convolution.  OG_E_RANGE if a folded weight is not finite.
+ * og_patchnet_forward: patches [n][32][32] (normalize != 0: raw patches, normalised here).  HardNet: out [n][128], L2-normalised.
+ *   AffNet: out [n][3] (tanh outputs, may be null) and lafs [n][2][3] updated in place (may be null): A = scale(A) A' rot(ori(A)),
+ *   A' = [[1 + x0, 0], [x1, 1 + x2]] / sqrt(det).  OriNet: out [n][2], lafs: A = A rot(atan2(y0 + 1e-8, y1 + 1e-8)).
+ *   rot(t) = [[cos t, sin t], [-sin t, cos t]]. */
+int og_patch_geometry(int32_t H, int32_t W, int32_t* out);
+size_t og_patch_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t n);
+int og_patch_pyramid(int32_t batch, int32_t H, int32_t W, const float* image, float* pyramid, void* workspace_dev, void* stream);
+int og_patch_extract(int32_t batch, int32_t H, int32_t W, int32_t n, const float* pyramid, const float* lafs, int32_t upright,
+                     int32_t normalize, float* patches, void* stream);
+size_t og_patchnet_packed_bytes(int32_t kind);
+int og_patchnet_pack(int32_t kind, float bn_eps, const float* const* params, void* packed_host);
+int og_patchnet_forward(int32_t kind, int32_t n, const float* patches, int32_t normalize, const void* packed_dev, float* out,
+                        float* lafs, void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,6 +184,13 @@ SYMBOLS = {
     "og_sift_describe": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_sift_select": (C.c_int, [_i32, _i32, _i32, _f, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_sift_gather": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_patch_geometry": (C.c_int, [_i32, _i32, C.POINTER(C.c_int32)]),
+    "og_patch_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "og_patch_pyramid": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "og_patch_extract": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "og_patchnet_packed_bytes": (_sz, [_i32]),
+    "og_patchnet_pack": (C.c_int, [_i32, _f, _vp, _vp]),
+    "og_patchnet_forward": (C.c_int, [_i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "og_adam_layout": (C.c_int, [_i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(og_adam_layout_t)]),
     "og_adam_step": (C.c_int, [_i32, C.POINTER(C.c_void_p), _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double,
                                C.c_double, C.c_double, _i32, C.c_double, _vp]),

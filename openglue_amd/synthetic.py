@@ -331,3 +331,35 @@ def make_superpoint_state_dict(batch_norm: bool = False, seed: int = 0, descript
             sd[f"{name}.running_var"] = 0.8 + 0.4 * torch.rand(c, generator=g)
             sd[f"{name}.num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
     return sd
+
+
+# ---------------------------------------------------------------- patch networks (openglue_amd/affnet_hardnet.py)
+def make_patchnet_state_dict(kind: str, seed: int = 0) -> "OrderedDict[str, torch.Tensor]":
+    """Seeded HardNet / AffNet / OriNet weights in kornia's state-dict layout (`features.{i}.*`): convolutions with PyTorch's default
+    init (uniform in +-1 / sqrt(fan_in), weights and the bias of features.19), BatchNorm running_mean ~ N(0, 0.1^2) and running_var ~
+    U(0.75, 1.25), so that no BatchNorm is an identity."""
+    if kind not in ("hardnet", "affnet", "orinet"):
+        raise ValueError(f"kind must be hardnet, affnet or orinet, got {kind!r}")
+    g = torch.Generator().manual_seed(1000 * seed + {"hardnet": 1, "affnet": 2, "orinet": 3}[kind])
+    c = 32 if kind == "hardnet" else 16
+    nout = {"hardnet": 128, "affnet": 3, "orinet": 2}[kind]
+    sd: "OrderedDict[str, torch.Tensor]" = OrderedDict()
+
+    def conv(i, cout, cin, k, bias):
+        bound = 1.0 / math.sqrt(cin * k * k)
+        sd[f"features.{i}.weight"] = (torch.rand(cout, cin, k, k, generator=g) * 2 - 1) * bound
+        if bias:
+            sd[f"features.{i}.bias"] = (torch.rand(cout, generator=g) * 2 - 1) * bound
+
+    def bn(i, ch):
+        sd[f"features.{i}.running_mean"] = torch.randn(ch, generator=g) * 0.1
+        sd[f"features.{i}.running_var"] = 0.75 + 0.5 * torch.rand(ch, generator=g)
+        sd[f"features.{i}.num_batches_tracked"] = torch.tensor(0, dtype=torch.int64)
+
+    for i, (cin, cout) in zip((0, 3, 6, 9, 12, 15), [(1, c), (c, c), (c, 2 * c), (2 * c, 2 * c), (2 * c, 4 * c), (4 * c, 4 * c)]):
+        conv(i, cout, cin, 3, False)
+        bn(i + 1, cout)
+    conv(19, nout, 4 * c, 8, kind != "hardnet")
+    if kind == "hardnet":
+        bn(20, 128)
+    return sd
