@@ -1,4 +1,4 @@
-"""Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py) and the
+"""Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py, tests/test_gpu_gemm_forms.py) and the
 form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
 their own.
 
@@ -13,6 +13,7 @@ import re
 import torch
 
 ATTENTION_FORWARD = ("attention_kernel<", "attention_dma_kernel<", "attention_p16_kernel<")
+GEMM = ("gemm_nt_f32_kernel<", "gemm_nt_f16x3_kernel<", "gemm_nt_f16x3_big_kernel<", "gemm_nt_f16x3_big2_kernel<")
 
 
 def short_name(name: str) -> str:
@@ -58,3 +59,8 @@ def launched_kernels(fn) -> list:
 def attention_instances(names) -> set:
     """The attention forward instances among `names`."""
     return {n for n in names if n.startswith(ATTENTION_FORWARD)}
+
+
+def gemm_instances(names) -> set:
+    """The exact-fp32 and split-f16 GEMM instances (csrc/gemm_f32.hip, csrc/gemm_f16x3.hip) among `names`."""
+    return {n for n in names if n.startswith(GEMM)}
