@@ -1,4 +1,4 @@
-"""Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py, tests/test_gpu_gemm_forms.py) and the
+"""Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py, tests/test_gpu_gemm_forms.py, tests/test_gpu_proj_mlp_forms.py) and the
 form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
 their own.
 
@@ -14,6 +14,7 @@ import torch
 
 ATTENTION_FORWARD = ("attention_kernel<", "attention_dma_kernel<", "attention_p16_kernel<")
 GEMM = ("gemm_nt_f32_kernel<", "gemm_nt_f16x3_kernel<", "gemm_nt_f16x3_big_kernel<", "gemm_nt_f16x3_big2_kernel<")
+PROJ_MLP = ("mlp_small_kernel<", "mlp_fused_kernel<", "proj_small_kernel<", "proj_stream_kernel<")
 
 
 def short_name(name: str) -> str:
@@ -64,3 +65,8 @@ def attention_instances(names) -> set:
 def gemm_instances(names) -> set:
     """The exact-fp32 and split-f16 GEMM instances (csrc/gemm_f32.hip, csrc/gemm_f16x3.hip) among `names`."""
     return {n for n in names if n.startswith(GEMM)}
+
+
+def proj_mlp_instances(names) -> list:
+    """The message-MLP and q | k | v projection launches (csrc/mlp_fused.hip) among `names`, in launch order, one entry per launch."""
+    return [n for n in names if n.startswith(PROJ_MLP)]
