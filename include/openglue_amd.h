@@ -296,7 +296,10 @@ int og_gemm_nt_f16x3_reshl(const void* A, int64_t lda, const void* B, int64_t ld
  * 128-token workgroups, the x fragments in registers, weights through an LDS ring) -- og_proj_block_pack writes its stream behind the small-batch
  * one.  OG_PROJ_STREAM=0 / 1 forces either kernel.  ABI v10: N (the row count of W the stream was packed for) is an argument -- it locates the batch
  * stream behind the small-batch one; before, it was read off ldy, which silently mis-addressed the stream for an output plane padded beyond N.
- * ldy >= N, a multiple of 64 halves for the batch kernel. */
+ * ldy >= N, a multiple of 64 halves for the batch kernel.  At K = 256, launches of more than 8192 rows whose planes are exactly as wide as the matrix
+ * (ldy == N, og_forward's own geometry), whose column ranges are whole 256-column slabs (a0 .. b1 multiples of 8) and whose split_row is a multiple
+ * of 32 take the weight-stationary kernel og_forward runs for 256-d batches (csrc/proj_wstat.hip: proj_wstat_kernel; it reads the small-batch
+ * stream, nothing more is packed); OG_PROJ_STREAM = 0 / 1 keeps such a launch on the kernels above. */
 size_t og_proj_block_stream_bytes(int32_t N, int32_t K);
 int og_proj_block_pack(int32_t N, int32_t K, const float* W, void* stream_host);
 int og_proj_block(const void* x_rows, int64_t ld, int32_t M, int32_t K, int32_t N, const void* stream_dev, const float* bias, const float* inv_scale_dev,

@@ -18,7 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libopenglue_amd.so")
-SOURCES = ["gemm_f32.hip", "gemm_f16x3.hip", "mlp_fused.hip", "attention.hip", "attention_train.hip", "linear_attention.hip", "sinkhorn.hip", "sinkhorn_resident.hip", "sinkhorn_train.hip", "batchnorm_train.hip", "matches.hip", "features.hip", "supervision.hip", "metrics.hip", "geometry.hip", "superpoint.hip", "sift.hip", "patchnet.hip", "optimizer.hip", "api.hip"]
+SOURCES = ["gemm_f32.hip", "gemm_f16x3.hip", "mlp_fused.hip", "proj_wstat.hip", "attention.hip", "attention_train.hip", "linear_attention.hip", "sinkhorn.hip", "sinkhorn_resident.hip", "sinkhorn_train.hip", "batchnorm_train.hip", "matches.hip", "features.hip", "supervision.hip", "metrics.hip", "geometry.hip", "superpoint.hip", "sift.hip", "patchnet.hip", "optimizer.hip", "api.hip"]
 ARCH = "gfx950"
 
 
@@ -50,7 +50,7 @@ def _stale(target: str, deps) -> bool:
 def build(force: bool = False, debug: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "og_common.h"), os.path.join(CSRC, "og_ransac.h"), os.path.join(os.path.dirname(HERE), "include", "openglue_amd.h")]
+    headers = [os.path.join(CSRC, "og_common.h"), os.path.join(CSRC, "og_ransac.h"), os.path.join(CSRC, "og_proj_deal.h"), os.path.join(os.path.dirname(HERE), "include", "openglue_amd.h")]
     flags = list(FLAGS)
     if debug:
         flags += ["-g", "-save-temps=obj"]

@@ -611,8 +611,22 @@ int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_
         return og_launch_proj_stream(XO + r0 * D4, D4, (int)R, D, (const char*)(lw + L.o_wqkvb), lw + L.o_bqkv, lw + L.o_scale,
                                      QKVh + r0 * QW, QKVl + r0 * QW, QW, split_row, a0 / 128, a1 / 128, b0 / 128, b1 / 128, st);
     };
+    // Batches of the 256-d family: proj_wstat_kernel (proj_wstat.hip), one 256-column slab -- q, k or v -- per workgroup with its weights in registers
+    // (the fragment-major copy proj_small_kernel reads), the token rows streaming through an LDS ring.  Uniform batches only.
+    // og_forward takes it from 8 units (32-token block x slab) per workgroup on -- 2048 units, the smallest launch it was measured at (C2's k | v of
+    // image 0: 1024 blocks x 2 slabs): a workgroup first loads 256 KB of weights, which a run of a few blocks does not pay back, so shorter launches
+    // keep the tile GEMM (the stage entry og_proj_block reaches the kernel from 8193 rows on).
+    auto proj_wstat_ok = [&](int64_t R, int64_t units) {
+        return L.o_wqkvs >= 0 && !favor && !rag && og_proj_wstat_wanted(R, D) && WQ == 256 && QW % 8 == 0 && units >= 2048;
+    };
+    auto proj_wstat = [&](const float* lw, int64_t r0, int64_t R, int split_row, int a0, int a1, int b0, int b1) -> int {      // ranges in channels
+        Scope sc(prof, OG_STAGE_GEMM_F16X3);
+        return og_launch_proj_wstat(XO + r0 * D4, D4, (int)R, (const char*)(lw + L.o_wqkvs), lw + L.o_bqkv, lw + L.o_scale, QKVh + r0 * QW, QKVl + r0 * QW,
+                                    QW, split_row, a0 / 256, a1 / 256, b0 / 256, b1 / 256, st);
+    };
     auto qkv_proj = [&](const float* lw, int64_t r0, int64_t R, int c0, int c1) -> int {
         if (proj_small_ok(R) && c0 % 32 == 0 && c1 % 32 == 0) return proj_small(lw, r0, R, 0, 0, 0, c0 / 32, c1 / 32);
+        if (c0 % 256 == 0 && c1 % 256 == 0 && proj_wstat_ok(R, (R + 31) / 32 * ((c1 - c0) / 256))) return proj_wstat(lw, r0, R, 0, 0, 0, c0, c1);
         if (proj_stream_ok(R, c0 == 0 && c1 == QW) && c0 % 128 == 0 && c1 % 128 == 0 && ((r0 * QW * 2) % 128 == 0)) return proj_stream(lw, r0, R, 0, 0, 0, c0, c1);
         const int cut = favor ? 2 * WQ : c1;
         const int ca[2] = {c0, c0 < cut && cut < c1 ? cut : c1}, cb[2] = {ca[1], c1};
@@ -670,8 +684,12 @@ int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_
                 } else if (proj_stream_ok(T) && T0 % 128 == 0 && WQ % 128 == 0) {
                     if ((rc = proj_stream(lw, 0, T, (int)T0, 0, WQ, 0, QW))) return rc;
                 } else if (!favor && !rag && T < (int64_t)1 << 30 && og_gemm_f16x3_row_split_ok(g)) {
-                    Scope sc(prof, OG_STAGE_GEMM_F16X3);
-                    if ((rc = og_launch_gemm_f16x3(g, st))) return rc;
+                    if (proj_wstat_ok(T, T0 / 32 + (T1 + 31) / 32 * 3)) {          // 256-d: the same one launch on the weight-stationary kernel
+                        if ((rc = proj_wstat(lw, 0, T, (int)T0, 0, WQ, 0, QW))) return rc;
+                    } else {
+                        Scope sc(prof, OG_STAGE_GEMM_F16X3);
+                        if ((rc = og_launch_gemm_f16x3(g, st))) return rc;
+                    }
                 } else {
                     if ((rc = qkv_proj(lw, T0, T1, 0, QW))) return rc;
                     if ((rc = qkv_proj(lw, 0, T0, 0, WQ))) return rc;

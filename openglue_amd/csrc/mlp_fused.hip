@@ -1582,6 +1582,12 @@ extern "C" int og_proj_block(const void* x_rows, int64_t ld, int32_t M, int32_t 
     // batches: the 128-token kernel (its stream sits behind the small one, located by N: ABI v10) when the ranges are whole 128-channel groups
     // (the stage entry of BOTH kernels: above 8192 rows it runs proj_stream_kernel at either width, whatever og_forward prefers)
     static const int ps_mode = [] { const char* e = getenv("OG_PROJ_STREAM"); return e ? atoi(e) : -1; }();
+    // 256-d batches whose planes are as wide as the matrix (ldy == N, og_forward's own geometry) and whose ranges are whole 256-column slabs: the
+    // weight-stationary kernel og_forward runs there (proj_wstat.hip; it reads the small-batch stream)
+    if (ps_mode < 0 && og_proj_wstat_wanted(M, K) && ldy == N && !(a0 % 8) && !(a1 % 8) && !(b0 % 8) && !(b1 % 8) && !(ldy & 7) &&
+        !(split_row > 0 && split_row < M && (split_row % 32)) && !((uintptr_t)yh & 15) && !((uintptr_t)yl & 15))
+        return og_launch_proj_wstat((const _Float16*)x_rows, ld, M, (const char*)stream_dev, bias, inv_scale_dev, (_Float16*)yh, (_Float16*)yl, ldy, split_row,
+                                    a0 / 8, a1 / 8, b0 / 8, b1 / 8, (hipStream_t)stream);
     if ((ps_mode >= 0 ? ps_mode != 0 : M > 8192) && og_proj_stream_big_bytes(N, K) && !(a0 % 4) && !(a1 % 4) && !(b0 % 4) && !(b1 % 4) && a1 - a0 <= 32 && b1 - b0 <= 32 &&
         !(ldy & 63) && !(split_row > 0 && split_row < M && (split_row % MT)) && !((uintptr_t)yh & 127) && !((uintptr_t)yl & 127))
         return og_launch_proj_stream((const _Float16*)x_rows, ld, M, K, (const char*)stream_dev + og_proj_stream_bytes(N, K), bias, inv_scale_dev,

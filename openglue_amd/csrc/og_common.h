@@ -216,6 +216,11 @@ int og_launch_proj_stream(const _Float16* X, int64_t ld, int M, int K, const cha
                           _Float16* Ch, _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream);   // ranges in units of 128 channels
 int og_launch_proj_small(const _Float16* X, int64_t ld, int M, int K, const char* wstream, const float* bias, const float* scale_dev,
                          _Float16* Ch, _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream);
+// ... and for 256-d batches (proj_wstat.hip: proj_wstat_kernel, one 256-column slab per workgroup, the weights in registers, the tokens through an
+// LDS ring).  It reads the SAME stream as proj_small_kernel (og_pack_proj_stream: one 1 KiB A fragment per load).  Ranges in slabs of 256 columns.
+bool og_proj_wstat_wanted(int64_t M, int K);                  // more than 8192 rows at K = 256
+int og_launch_proj_wstat(const _Float16* X, int64_t ld, int M, const char* wstream, const float* bias, const float* scale_dev, _Float16* Ch,
+                         _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream);
 
 constexpr int OG_ATTN_COUNTERS = 256;                                   // (problem, head, query tile) triples of a key-split launch
 constexpr int64_t OG_ATTN_PARTIAL_FLOATS = (int64_t)512 * 4 * 34 * 64;     // 512 workgroups (two per CU) x 4 waves x (32 O registers + m + l) x 64 lanes

@@ -15,6 +15,7 @@ import torch
 ATTENTION_FORWARD = ("attention_kernel<", "attention_dma_kernel<", "attention_p16_kernel<")
 GEMM = ("gemm_nt_f32_kernel<", "gemm_nt_f16x3_kernel<", "gemm_nt_f16x3_big_kernel<", "gemm_nt_f16x3_big2_kernel<")
 PROJ_MLP = ("mlp_small_kernel<", "mlp_fused_kernel<", "proj_small_kernel<", "proj_stream_kernel<")
+PROJ_WSTAT = "proj_wstat_kernel"       # csrc/proj_wstat.hip: the weight-stationary q | k | v projection of 256-d batches (no template arguments)
 
 
 def short_name(name: str) -> str:

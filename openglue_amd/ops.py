@@ -138,7 +138,8 @@ def mlp_block(x: torch.Tensor, o: torch.Tensor, w0: torch.Tensor, b0: torch.Tens
 
 
 def proj_block(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, split_row: int = 0, cols_a=None, cols_b=None):
-    """The small-batch projection kernel (og_proj_block): y = x @ w.T + bias on token-major fp32 x [M, K], w [N, K], K = 256 or 128, N a multiple of 32.
+    """The projection stage entry (og_proj_block: proj_small_kernel up to 8192 rows; above, the batch kernels -- proj_wstat_kernel at K = 256 for ranges of
+    whole 256-column slabs, proj_stream_kernel otherwise): y = x @ w.T + bias on token-major fp32 x [M, K], w [N, K], K = 256 or 128, N a multiple of 32.
     Rows below split_row get the output columns cols_a = (c0, c1), the others cols_b (multiples of 32; default: all N); columns outside a
     row's range come back as zeros."""
     lib = _lib.load()
