@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""The reference's first training stage -- self-supervised homography pre-training (pretrain_homography.py,
+config/homography_pretraining.yaml, data/oxford_paris_dataset.py) -- from images, on openglue_amd:
+
+    uint8 frames --pairs.homography_pairs-->  image0, image1, H      (random corner displacements drawn on the device)
+    SIFT (or --features superpoint) on both views                 -> LAFs, responses, descriptors
+    examples/train_step.py training_step: prepare_features_output -> generate_gt_matches -> SuperGlue.train() -> criterion
+    backward -> openglue_amd.optim.Adam (clip + Adam + StepLR), the constants of examples/train_fit.py
+
+The frames are synthetic (synthetic.make_image, three grey renderings as R, G, B) and stand for what a loader hands over after
+decoding and resizing.  From there to the parameter update every tensor stays on the GPU: nothing is copied to the host between the
+frames and the optimizer step except the extractor's own keypoint count (one integer per image batch) and the numbers printed here.
+A fresh pair is synthesised from the same frames every step, as a data loader would.
+
+    python examples/pretrain_homography.py [--steps 5] [--pairs 2] [--size 240 320] [--offset 24] [--features sift|superpoint]"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from examples.train_fit import GAMMA, LR, MAX_GRAD_NORM                # noqa: E402
+from examples.train_step import MARGIN, training_step                  # noqa: E402
+from openglue_amd import optim, pairs, synthetic as syn                # noqa: E402
+from openglue_amd.sift import SIFT                                     # noqa: E402
+from openglue_amd.superglue import SuperGlue                           # noqa: E402
+from openglue_amd.superpoint import SuperPointNetBn                    # noqa: E402
+
+
+def make_frames(B, H, W, dev, seed=0):
+    """[B, H, W, 3] uint8 on the device"""
+    rgb = torch.stack([torch.cat([syn.make_image(H, W, seed=seed + 3 * b + c)[0] for c in range(3)]) for b in range(B)])
+    return (rgb * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous().to(dev)
+
+
+def make_extractor(name, keypoints, dev):
+    if name == "sift":
+        return SIFT(max_keypoints=keypoints), 128
+    sp = SuperPointNetBn(max_keypoints=keypoints, keypoint_threshold=0.005)
+    sp.load_state_dict(syn.make_superpoint_state_dict(True, seed=1))
+    return sp.eval().to(dev), 256
+
+
+def extract(extractor, item):
+    """the pair item -> the batch examples/train_step.py's training_step takes (cached-features layout)"""
+    batch = {"transformation": item["transformation"]}
+    for side in "01":
+        image = item["image" + side]
+        lafs, scores, desc = extractor(image)
+        batch.update({"lafs" + side: lafs, "scores" + side: scores, "descriptors" + side: desc,
+                      f"image{side}_size": [image.shape[3], image.shape[2]]})
+    return batch
+
+
+def run(steps=5, n_pairs=2, size=(240, 320), offset=24, feature="sift", keypoints=512, stages=3, seed=0, log=print):
+    """-> [(matched labels, total loss)] per step"""
+    dev = torch.device("cuda:0")
+    H, W = size
+    frames = make_frames(n_pairs, H, W, dev, seed)
+    extractor, dim = make_extractor(feature, keypoints, dev)
+    cfg = syn.make_config(descriptor_dim=dim, num_stages=stages, num_heads=4, num_iters=20, side_info_size=1)
+    model = SuperGlue(cfg)
+    model.load_state_dict(syn.make_state_dict(cfg, seed=0))
+    model = model.to(dev).train()
+    opt = optim.Adam(model.parameters(), lr=LR, max_grad_norm=MAX_GRAD_NORM, scheduler_gamma=GAMMA)
+    gen = torch.Generator(device=dev).manual_seed(seed)
+    history = []
+    for s in range(steps):
+        item = pairs.homography_pairs(frames, offset, generator=gen)
+        with torch.no_grad():
+            batch = extract(extractor, item)
+        opt.zero_grad(set_to_none=False)
+        out = training_step(model, batch, MARGIN, with_labels=True)
+        if out is None:                                   # an image without keypoints: the reference skips the batch too
+            log(f"step {s:2d}  no keypoints, skipped")
+            continue
+        total, lo, y_true = out
+        total.backward()
+        opt.step()
+        matched = int((y_true["gt_matches0"] >= 0).sum())
+        history.append((matched, float(total.detach())))
+        log(f"step {s:2d}  keypoints {batch['lafs0'].shape[1]} / {batch['lafs1'].shape[1]} per image  matched labels {matched}  "
+            f"loss {history[-1][1]:.4f}  nll {float(lo['loss']):.4f}  metric {float(lo['metric_loss']):.4f}")
+    return history
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--pairs", type=int, default=2)
+    ap.add_argument("--size", type=int, nargs=2, default=(240, 320), metavar=("H", "W"))
+    ap.add_argument("--offset", type=int, default=24)
+    ap.add_argument("--features", default="sift", choices=("sift", "superpoint"))
+    ap.add_argument("--keypoints", type=int, default=512)
+    a = ap.parse_args()
+    run(a.steps, a.pairs, tuple(a.size), a.offset, a.features, a.keypoints)

@@ -92,8 +92,9 @@ def make_pairs(B, N, D, kind, dev, seed=0):
     return cached
 
 
-def training_step(model, batch, margin=MARGIN):
-    """matching_module.py:70-105 with use_cached_features: the weighted loss and its two parts, or None without keypoints"""
+def training_step(model, batch, margin=MARGIN, with_labels=False):
+    """matching_module.py:70-105 with use_cached_features: the weighted loss and its two parts (with_labels: and the ground-truth
+    labels), or None without keypoints"""
     f0 = features.prepare_features_output(batch["lafs0"], batch["scores0"], batch["descriptors0"], "none")
     f1 = features.prepare_features_output(batch["lafs1"], batch["scores1"], batch["descriptors1"], "none")
     data, y_true = supervision.generate_gt_matches(batch, f0, f1, POS_THR, NEG_THR)
@@ -101,7 +102,8 @@ def training_step(model, batch, margin=MARGIN):
         return None
     y_pred = model(data)
     lo = supervision.criterion(y_true, y_pred, margin=margin)
-    return NLL_WEIGHT * lo["loss"] + METRIC_WEIGHT * lo["metric_loss"], lo
+    total = NLL_WEIGHT * lo["loss"] + METRIC_WEIGHT * lo["metric_loss"]
+    return (total, lo, y_true) if with_labels else (total, lo)
 
 
 def run(steps=20, pairs=2, kpts=512, dim=128, stages=3, lr=1e-3, transform="perspective", margin=MARGIN, log=print):

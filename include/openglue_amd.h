@@ -742,6 +742,39 @@ int og_patchnet_pack(int32_t kind, float bn_eps, const float* const* params, voi
 int og_patchnet_forward(int32_t kind, int32_t n, const float* patches, int32_t normalize, const void* packed_dev, float* out,
                         float* lafs, void* workspace_dev, void* stream);
 
+/* ABI v14, additive -- homography training pairs (csrc/pairs.hip): the arithmetic of the reference's self-supervised data items,
+ * OxfordParis1MDataset.__getitem__ (data/oxford_paris_dataset.py:27-66) and MegaDepthWarpingDataset.__getitem__
+ * (data/megadepth_dataset.py:33-52): cv2.getPerspectiveTransform, cv2.warpPerspective (bilinear, constant border 0), crop, grey, / 255.
+ * Device pointers only, no host synchronisation, no allocation; every result is bit-identical from run to run and independent of the
+ * batch it is computed in.  tests/pairs_ref.py is the specification.  Limits: 1 <= batch <= 65535, 1 <= H, W <= 32768, C in {1, 3};
+ * anything else returns OG_E_SHAPE, a null pointer OG_E_INVALID, a matrix pointer that is not 8-byte aligned OG_E_ALIGN.
+ *
+ * og_perspective_transform: src, dst [batch][4][2] float -> M [batch][3][3] double with M (x, y, 1) ~ (u, v, 1) for the four pairs.
+ *   Point i gives row i = [x y 1 0 0 0 -xu -yu | u] and row i + 4 = [0 0 0 x y 1 -xv -yv | v]; the 8 x 8 system is solved in fp64 by
+ *   Gaussian elimination with partial pivoting (first largest |entry| of the column) and back substitution, M[2][2] = 1.  A pivot that
+ *   is not above 1e-12 times the largest |coefficient| of the system (zero at the level of rounding), or a non-finite result: M = 0.
+ * og_warp_perspective_u8: src [batch][H][W][C] bytes, M [batch][3][3] double (source -> destination, as cv2.warpPerspective without
+ *   WARP_INVERSE_MAP) -> dst [batch][h][w][C]: the window with origin (x0, y0) and size w x h of the H x W destination frame
+ *   (0 <= x0, x0 + w <= W, 0 <= y0, y0 + h <= H, else OG_E_SHAPE).  Per image Mi = adj(M) * (1 / det M) in fp64 (Mi = 0 when det = 0);
+ *   per destination pixel (x, y), every fp64 operation rounded on its own:
+ *     Wd = (Mi20 x + Mi21 y) + Mi22;  s = Wd != 0 ? 32 / Wd : 0;  fX = ((Mi00 x + Mi01 y) + Mi02) s, fY likewise;
+ *     fX > INT_MAX -> INT_MAX, not (fX >= INT_MIN) -> INT_MIN;  X = rint(fX) (half to even), Y likewise;
+ *     sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31; taps (sy, sx), (sy, sx + 1), (sy + 1, sx), (sy + 1, sx + 1), 0 outside the
+ *     source, integer weights 32 (32 - fx)(32 - fy), 32 fx (32 - fy), 32 (32 - fx) fy, 32 fx fy (sum 32768);
+ *     out = (sum w v + 16384) >> 15 per channel.
+ * og_homography_pairs: frames [batch][H][W][C] bytes, warp_offset [batch][4][2] float -> image0, image1 [batch][1][h][w] float with
+ *   h = H - 2 offset, w = W - 2 offset (offset >= 0, 2 offset < min(H, W)), H_true [batch][3][3] float.  With the corners c =
+ *   (o, o), (o, H-o-1), (W-o-1, o), (W-o-1, H-o-1): H_warp = transform(c + warp_offset -> c) stays in fp64 in workspace_dev (9 batch
+ *   doubles, 8-byte aligned) and drives the warp; H_true = transform(c - o + warp_offset -> c - o) rounded to float.  One launch solves
+ *   both systems of every pair, one launch writes both views: image0 = grey(frame window) / 255.f, image1 = grey(warp window) / 255.f,
+ *   grey(R, G, B) = (9798 R + 19235 G + 3735 B + 16384) >> 15 on the bytes after the warp (C = 1: the byte itself).
+ *   warp_offset == NULL: workspace_dev already holds the batch warp matrices, nothing is solved and H_true is not written (may be NULL). */
+int og_perspective_transform(int32_t batch, const float* src, const float* dst, double* M, void* stream);
+int og_warp_perspective_u8(int32_t batch, int32_t H, int32_t W, int32_t C, const uint8_t* src, const double* M, int32_t x0, int32_t y0,
+                           int32_t w, int32_t h, uint8_t* dst, void* stream);
+int og_homography_pairs(int32_t batch, int32_t H, int32_t W, int32_t C, const uint8_t* frames, int32_t offset, const float* warp_offset,
+                        float* image0, float* image1, float* H_true, void* workspace_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

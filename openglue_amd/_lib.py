@@ -194,6 +194,9 @@ SYMBOLS = {
     "og_adam_layout": (C.c_int, [_i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(og_adam_layout_t)]),
     "og_adam_step": (C.c_int, [_i32, C.POINTER(C.c_void_p), _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double,
                                C.c_double, C.c_double, _i32, C.c_double, _vp]),
+    "og_perspective_transform": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
+    "og_warp_perspective_u8": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "og_homography_pairs": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
