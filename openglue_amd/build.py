@@ -50,7 +50,7 @@ def _stale(target: str, deps) -> bool:
 def build(force: bool = False, debug: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIB_DIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "og_common.h"), os.path.join(CSRC, "og_ransac.h"), os.path.join(CSRC, "og_proj_deal.h"), os.path.join(os.path.dirname(HERE), "include", "openglue_amd.h")]
+    headers = [os.path.join(CSRC, h) for h in sorted(os.listdir(CSRC)) if h.endswith(".h")] + [os.path.join(os.path.dirname(HERE), "include", "openglue_amd.h")]
     flags = list(FLAGS)
     if debug:
         flags += ["-g", "-save-temps=obj"]

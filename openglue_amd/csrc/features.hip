@@ -8,7 +8,7 @@
 //  * og_compact_matches: inference.py:192-209 -- the valid matches of a batch in (pair, keypoint) order with
 //    their confidence, the matched LAFs of both images and the keypoint centres (kornia get_laf_center =
 //    LAF[..., 2]).  Order-preserving compaction: per-256 counts, one scan block, scatter.
-#include "og_common.h"
+#include "og_block.h"
 
 namespace {
 
@@ -41,27 +41,15 @@ __global__ __launch_bounds__(256) void prepare_features_kernel(const float* __re
 __global__ __launch_bounds__(256) void compact_count_kernel(const int64_t* __restrict__ matches0, int64_t total,
                                                             int* __restrict__ block_counts) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const bool v = i < total && matches0[i] >= 0;
-    const unsigned long long bal = __ballot(v);
     __shared__ int wc[4];
-    if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+    int cnt;
+    block_rank_of(i < total && matches0[i] >= 0, wc, cnt);
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = cnt;
 }
 
 // exclusive scan of the block counts by ONE workgroup (<= a few thousand blocks); total -> count_out
 __global__ __launch_bounds__(256) void compact_scan_kernel(int* __restrict__ block_counts, int nblocks, int* __restrict__ count_out) {
-    __shared__ int part[256];
-    const int tid = threadIdx.x;
-    const int per = (nblocks + 255) / 256;
-    int s = 0;
-    for (int k = 0; k < per; ++k) { const int i = tid * per + k; if (i < nblocks) s += block_counts[i]; }
-    part[tid] = s;
-    __syncthreads();
-    if (tid == 0) { int acc = 0; for (int i = 0; i < 256; ++i) { const int v = part[i]; part[i] = acc; acc += v; } *count_out = acc; }
-    __syncthreads();
-    int acc = part[tid];
-    for (int k = 0; k < per; ++k) { const int i = tid * per + k; if (i < nblocks) { const int v = block_counts[i]; block_counts[i] = acc; acc += v; } }
+    block_exclusive_scan_inplace(block_counts, nblocks, count_out);
 }
 
 __global__ __launch_bounds__(256) void compact_scatter_kernel(const int64_t* __restrict__ matches0, const float* __restrict__ ms0,
@@ -71,16 +59,13 @@ __global__ __launch_bounds__(256) void compact_scatter_kernel(const int64_t* __r
                                                               float* __restrict__ conf, float* __restrict__ ml0, float* __restrict__ ml1,
                                                               float* __restrict__ k0, float* __restrict__ k1) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t mj = i < total ? matches0[i] : -1;
     const bool v = mj >= 0;
-    const unsigned long long bal = __ballot(v);
     __shared__ int wc[4];
-    if (lane == 0) wc[wave] = __popcll(bal);
-    __syncthreads();
+    int cnt;
+    const int rank = block_rank_of(v, wc, cnt);
     if (!v) return;
-    int pos = block_off[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) pos += wc[w];
+    const int pos = block_off[blockIdx.x] + rank;
     const int64_t b = i / M, q = i - b * M;
     idxs[2 * (int64_t)pos] = q; idxs[2 * (int64_t)pos + 1] = mj;
     batch[pos] = b;

@@ -246,17 +246,6 @@ static FundWs fund_layout(void* ws, int B, int m, int H) {
     return w;
 }
 
-// every lane gets the sum over the workgroup: lanes (butterfly), then waves in order
-__device__ inline double block_sum_double(double v, double* red) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 __global__ void __launch_bounds__(256) fm_prep_kernel(FGeo g, FundWs w) {
     __shared__ int wsum[4];
     __shared__ double red[4];
@@ -278,7 +267,7 @@ __global__ void __launch_bounds__(256) fm_prep_kernel(FGeo g, FundWs w) {
     const double inv_n = n > 0 ? 1.0 / (double)n : 0.0;
     double cen[4];
 #pragma unroll
-    for (int c = 0; c < 4; ++c) cen[c] = block_sum_double(s[c], red) * inv_n;
+    for (int c = 0; c < 4; ++c) cen[c] = block_sum(s[c], red) * inv_n;
     double d[2] = {0.0, 0.0};
     for (int k = threadIdx.x; k < n; k += 256) {
         const double4 q = pixel(k);
@@ -288,7 +277,7 @@ __global__ void __launch_bounds__(256) fm_prep_kernel(FGeo g, FundWs w) {
     double sc[2];
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-        const double mean = block_sum_double(d[c], red) * inv_n;
+        const double mean = block_sum(d[c], red) * inv_n;
         const double v = M_SQRT2 / mean;
         sc[c] = (mean > 0.0 && finite(v)) ? v : 1.0;              // every point on the centroid: leave the scale alone
     }
@@ -350,8 +339,6 @@ __device__ __forceinline__ bool sampson_inlier_px(const float (&e)[9], float4 q,
     return __fdiv_rn(__fmul_rn(num, num), den) <= t2;
 }
 
-__device__ __forceinline__ float4 to_f4(double4 d) { return make_float4((float)d.x, (float)d.y, (float)d.z, (float)d.w); }
-
 __global__ void __launch_bounds__(256) fm_score_kernel(FundWs w, int m, int H, int groups, float t2) {
     __shared__ float4 pts[kFChunk];
     const int b = blockIdx.x / groups;                       // `groups` workgroups per pair, pair-major along x
@@ -373,13 +360,8 @@ __global__ void __launch_bounds__(256) fm_score_kernel(FundWs w, int m, int H, i
         if (live)
             for (int k = 0; k < len; ++k) inl += sampson_inlier_px(e, pts[k], s0sq, s1sq, t2);
     }
-    unsigned long long key = live ? ((unsigned long long)(inl + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)model) : 0ull;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o, 64);
-        key = other > key ? other : key;
-    }
-    if ((threadIdx.x & 63) == 0 && key) atomicMax(&w.best[b], key);
+    const unsigned long long key = live ? ((unsigned long long)(inl + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)model) : 0ull;
+    publish_best(key, &w.best[b]);
 }
 
 __host__ __device__ constexpr int tri(int i, int j) { return i <= j ? i * 9 - i * (i - 1) / 2 + (j - i) : j * 9 - j * (j - 1) / 2 + (i - j); }
@@ -481,7 +463,7 @@ __global__ void __launch_bounds__(256) fm_finish_kernel(FGeo g, FundWs w, int H,
     auto count_inliers = [&](const float (&f)[9]) {
         int c = 0;
         for (int k = threadIdx.x; k < n; k += 256) c += sampson_inlier_px(f, to_f4(P[k]), s0sq, s1sq, t2);
-        return block_sum_int(c, red);
+        return block_sum(c, red);
     };
     int cur = count_inliers(e);
     for (int round = 0; round < refine; ++round) {

@@ -26,7 +26,7 @@
 //                         checks spread over lanes, errors against the ground truth
 //    Every launch count is fixed: 5 kernels whatever the batch.
 #include "og_common.h"
-#include "og_ransac.h"      // finite, pmul, peval, mix64, draw_distinct, block_sum_int, jacobi3
+#include "og_ransac.h"      // finite, pmul, peval, mix64, draw_distinct, to_f4, publish_best, jacobi3; og_block.h: block_sum
 
 namespace {
 
@@ -567,8 +567,8 @@ __global__ void __launch_bounds__(256) precision_kernel(Geo g, double threshold,
         ++matched;
         correct += d < threshold;
     }
-    matched = block_sum_int(matched, red);
-    correct = block_sum_int(correct, red);
+    matched = block_sum(matched, red);
+    correct = block_sum(correct, red);
     if (threadIdx.x == 0) {
         const int det = g.nk0 ? min(g.nk0[b], g.m) : g.m;
         precision[b] = matched > 0 ? (float)correct / (float)matched : 0.0f;
@@ -606,8 +606,6 @@ __device__ __forceinline__ bool sampson_inlier(const float (&e)[9], float4 q, fl
     return __fdiv_rn(__fmul_rn(num, num), den) <= t2;
 }
 
-__device__ __forceinline__ float4 to_f4(double4 d) { return make_float4((float)d.x, (float)d.y, (float)d.z, (float)d.w); }
-
 constexpr int kScoreChunk = 1024;
 
 __global__ void __launch_bounds__(256) score_kernel(PoseWs w, int m, int H) {
@@ -631,13 +629,8 @@ __global__ void __launch_bounds__(256) score_kernel(PoseWs w, int m, int H) {
         if (live)
             for (int k = 0; k < len; ++k) inl += sampson_inlier(e, pts[k], t2);
     }
-    unsigned long long key = live ? ((unsigned long long)(inl + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)model) : 0ull;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long other = __shfl_xor(key, o, 64);
-        key = other > key ? other : key;
-    }
-    if ((threadIdx.x & 63) == 0 && key) atomicMax(&w.best[b], key);
+    const unsigned long long key = live ? ((unsigned long long)(inl + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)model) : 0ull;
+    publish_best(key, &w.best[b]);
 }
 
 __device__ inline double det3(const double (&M)[3][3]) {
@@ -746,9 +739,9 @@ __global__ void __launch_bounds__(256) finish_kernel(Geo g, PoseWs w, int H, flo
         inliers[(int64_t)b * g.m + i] = f ? 1 : 0;
         inl += f;
     }
-    inl = block_sum_int(inl, red);
+    inl = block_sum(inl, red);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) pos[k] = block_sum_int(pos[k], red);
+    for (int k = 0; k < 4; ++k) pos[k] = block_sum(pos[k], red);
     if (threadIdx.x != 0) return;
     num_inliers[b] = inl;
     if (!have) {

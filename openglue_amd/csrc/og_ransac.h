@@ -1,7 +1,8 @@
 // Helpers the two RANSAC units share (metrics.hip: five-point / essential matrix, geometry.hip: seven-point / fundamental matrix).
 // Internal, not part of the ABI.  Everything lives in the unnamed namespace of the including unit, as it did in metrics.hip.
+// The workgroup sum and the compaction rank come from og_block.h.
 #pragma once
-#include "og_common.h"
+#include "og_block.h"
 
 namespace {
 
@@ -51,18 +52,6 @@ __host__ __device__ inline void draw_distinct(uint64_t seed, uint64_t pair, int 
     }
 }
 
-__device__ inline int block_sum_int(int v, int* red) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if (lane == 0) red[wid] = v;
-    __syncthreads();
-    int t = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
-    return t;
-}
-
 // The validity rule of both units: keypoint i of pair b is matched when i < num_keypoints0[b] and 0 <= matches0[i] < n.  G carries
 // matches0 [B][m] int64, nk0 [B] (or null: m), m and n.
 template <class G>
@@ -78,24 +67,32 @@ __device__ inline bool valid_match(const G& g, int b, int i, int& j) {
 // barrier orders the writes to idx before whatever the workgroup reads from it afterwards.
 template <class G, class Each>
 __device__ inline int compact_valid_matches(const G& g, int b, int* idx, int* wsum, Each each) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     int base = 0;
     for (int i0 = 0; i0 < g.m; i0 += 256) {
         const int i = i0 + threadIdx.x;
         int j = 0;
         const bool v = i < g.m && valid_match(g, b, i, j);
         if (v) each(i, j);
-        const unsigned long long bal = __ballot(v);
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wid] = __popcll(bal);
-        __syncthreads();
-        int off = base;
-        for (int q = 0; q < wid; ++q) off += wsum[q];
-        if (v) idx[off + before] = i;
-        base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+        int cnt;
+        const int rank = block_rank_of(v, wsum, cnt);
+        if (v) idx[base + rank] = i;
+        base += cnt;
         __syncthreads();
     }
     return base;
+}
+
+__device__ __forceinline__ float4 to_f4(double4 d) { return make_float4((float)d.x, (float)d.y, (float)d.z, (float)d.w); }
+
+// The tail of both score kernels: a thread's key is (inliers + 1) << 32 | ~model, 0 for "no model"; the wave's largest goes into
+// the pair's winner by one 64-bit atomicMax (more inliers win, then the lower model index).
+__device__ __forceinline__ void publish_best(unsigned long long key, unsigned long long* best) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(key, o, 64);
+        key = other > key ? other : key;
+    }
+    if ((threadIdx.x & 63) == 0 && key) atomicMax(best, key);
 }
 
 // symmetric 3 x 3 eigen-decomposition by cyclic Jacobi: A = V diag(A) V^T on return

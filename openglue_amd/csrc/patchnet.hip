@@ -11,12 +11,13 @@
 //                32 x 32 map, 8 rows of a 16 x 16 map, or two whole 8 x 8 maps; wave w owns pixels 32 w .. 32 w + 31 (whole rows of
 //                ONE patch) and Cout / 32 accumulator tiles.  The input rows with their halo are staged in LDS KC channels at a time,
 //                a pixel outside its own patch is zero (never the neighbouring patch); the K loop runs over 9 taps x KC channels
-//                reading A fragments at tap offsets, stride 1 or 2.  Weights are fragment-major with BatchNorm folded; ReLU in the
+//                reading A fragments at tap offsets, stride 1 or 2.  Weights are fragment-major (pack_fragments of og_conv_f32.h, shared with
+//                superpoint.hip) with BatchNorm folded; ReLU in the
 //                epilogue.  Cout = 16 runs as a 32-wide tile whose upper half is zero weights.
 //   tail         the 8 x 8 convolution is a [n, 64 C] x [64 C, Cout] product.  HardNet: MFMA, a workgroup owns 32 patches x 32
 //                channels, its 4 waves a quarter of K each, summed in LDS in wave order; then BN(20) as a bias and a row L2
 //                normalisation.  AffNet / OriNet (3 / 2 outputs): one wave per patch, VALU, then bias, tanh and the LAF update.
-#include "og_common.h"
+#include "og_conv_f32.h"
 #include <cmath>
 
 namespace {
@@ -523,33 +524,21 @@ extern "C" int og_patchnet_pack(int32_t kind, float bn_eps, const float* const* 
         put(N.b0 + co, -(double)params[1][co] * sc);
     }
     for (int l = 0; l < 5; ++l) {
-        const int Cin = N.cin[l], Cout = N.cout[l], kc = pn_kc(Cin, N.stride[l]), nsteps = 9 * Cin / 8, spc = 9 * (kc / 8);
+        const int Cin = N.cin[l], Cout = N.cout[l], kc = pn_kc(Cin, N.stride[l]);
         const float* w = params[3 * (l + 1)];
-        for (int co = 0; co < Cout; ++co) {
-            const double sc = scale(l + 1, co);
-            put(N.b[l] + co, -(double)params[3 * (l + 1) + 1][co] * sc);
-            for (int s = 0; s < nsteps; ++s) {
-                const int chunk = s / spc, tap = (s % spc) / (kc / 8), kk = s % (kc / 8);
-                for (int h = 0; h < 2; ++h)
-                    for (int e = 0; e < 4; ++e) {
-                        const int ci = chunk * kc + kk * 8 + 4 * h + e;
-                        put(N.w[l] + (((int64_t)(co / 32) * nsteps + s) * 64 + (co & 31) + 32 * h) * 4 + e,
-                            (double)w[((int64_t)co * Cin + ci) * 9 + tap] * sc);
-                    }
-            }
-        }
+        for (int co = 0; co < Cout; ++co) put(N.b[l] + co, -(double)params[3 * (l + 1) + 1][co] * scale(l + 1, co));
+        pack_fragments(put, N.w[l], Cout, Cout < 32 ? 32 : Cout, 9 * Cin, [&](int co, int k) {
+            int ci, tap;
+            conv3x3_k(k, kc, ci, tap);
+            return (double)w[((int64_t)co * Cin + ci) * 9 + tap] * scale(l + 1, co);
+        });
     }
     const int C = N.c[2], K = 64 * C;
     const float* wt = params[18];
     if (kind == PN_HARDNET) {
-        for (int co = 0; co < 128; ++co) {
-            const double sc = 1.0 / std::sqrt((double)params[20][co] + (double)bn_eps);
-            put(N.bt + co, -(double)params[19][co] * sc);
-            for (int k = 0; k < K; ++k) {
-                const int c = k % C, pos = k / C, s = k / 8, h = (k % 8) / 4, e = k % 4;
-                put(N.wt + (((int64_t)(co / 32) * (K / 8) + s) * 64 + (co & 31) + 32 * h) * 4 + e, (double)wt[((int64_t)co * C + c) * 64 + pos] * sc);
-            }
-        }
+        auto tail_scale = [&](int co) { return 1.0 / std::sqrt((double)params[20][co] + (double)bn_eps); };
+        for (int co = 0; co < 128; ++co) put(N.bt + co, -(double)params[19][co] * tail_scale(co));
+        pack_fragments(put, N.wt, 128, 128, K, [&](int co, int k) { return (double)wt[((int64_t)co * C + k % C) * 64 + k / C] * tail_scale(co); });
     } else {
         for (int co = 0; co < N.nout; ++co) {
             put(N.bt + co, params[19][co]);

@@ -19,7 +19,7 @@
 //             higher-ranked points (count, scan, fill), then rounds to the fixed point of "kept iff no kept higher-ranked neighbour";
 //             top-k; min_stack over the batch.
 //   gather    LAFs (lafs_from_opencv_kpts, mr_size 6), scores and descriptors of the kept keypoints in output order.
-#include "og_common.h"
+#include "og_block.h"
 #include <cmath>
 
 namespace {
@@ -251,35 +251,11 @@ __global__ __launch_bounds__(256) void sift_extrema_kernel(const float* __restri
     if (tid == 0) seg[(int64_t)b * segtot + segbase + row * gridDim.x + s] = cnt;
 }
 
-// exclusive scan of a[b * stride + 0 .. n) in place (n = n_fixed, or min(n_dev[b], ncap)), total -> total[b]
+// exclusive scan of a[b * stride + 0 .. n) in place (n = n_fixed, or min(n_dev[b], ncap)), total -> total[b]; the body is og_block.h's
 __global__ __launch_bounds__(256) void sift_scan_kernel(int32_t* __restrict__ a, int64_t stride, int n_fixed, const int32_t* __restrict__ n_dev,
                                                         int ncap, int32_t* __restrict__ total) {
-    __shared__ int32_t part[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int n = n_dev ? min(n_dev[b], ncap) : n_fixed;
-    int32_t* ab = a + (int64_t)b * stride;
-    const int per = (n + 255) / 256;
-    const int lo = min(tid * per, n), hi = min(lo + per, n);
-    int sum = 0;
-    for (int i = lo; i < hi; ++i) sum += ab[i];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int i = 0; i < 256; ++i) {
-            const int v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        total[b] = run;
-    }
-    __syncthreads();
-    int run = part[tid];
-    for (int i = lo; i < hi; ++i) {
-        const int v = ab[i];
-        ab[i] = run;
-        run += v;
-    }
+    const int b = blockIdx.x;
+    block_exclusive_scan_inplace(a + (int64_t)b * stride, n_dev ? min(n_dev[b], ncap) : n_fixed, total + b);
 }
 
 // the flagged samples of one segment, refined again and written at the segment's scanned offset in column order
@@ -288,16 +264,14 @@ __global__ __launch_bounds__(256) void sift_compact_kernel(const float* __restri
                                                            int segbase, int cap, int32_t* __restrict__ det_i, double* __restrict__ det_f) {
     __shared__ int wsum[4];
     const int rows = h - 2 * SIFT_BORDER;
-    const int s = blockIdx.x, row = blockIdx.y, b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l = 1 + row / rows, r = SIFT_BORDER + row % rows, c = s * SIFT_SEG + tid;
+    const int s = blockIdx.x, row = blockIdx.y, b = blockIdx.z;
+    const int l = 1 + row / rows, r = SIFT_BORDER + row % rows, c = s * SIFT_SEG + (int)threadIdx.x;
     const int64_t ls = (int64_t)h * w;
     const bool keep = c >= SIFT_BORDER && c < w - SIFT_BORDER && mask[(int64_t)b * dtot + doff + l * ls + (int64_t)r * w + c];
-    const uint64_t bal = __ballot(keep);
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
+    int cnt;
+    const int rank = block_rank_of(keep, wsum, cnt);
     if (!keep) return;
-    int off = seg[(int64_t)b * segtot + segbase + row * gridDim.x + s] + __popcll(bal & ((1ull << lane) - 1));
-    for (int i = 0; i < wave; ++i) off += wsum[i];
+    const int off = seg[(int64_t)b * segtot + segbase + row * gridDim.x + s] + rank;
     if (off >= cap) return;                       // reported: counts[b] > capacity
     SiftRefined q;
     if (!sift_refine(dog + (int64_t)b * dtot + doff, h, w, o, l, r, c, q)) return;      // cannot happen: the flag says it converged

@@ -6,18 +6,21 @@
 //   conv1a       1 -> 64, VALU, one thread per (pixel, 4 channels)                                  full resolution
 //   conv3x3      implicit GEMM: a workgroup owns 8 x 16 output pixels x BN channels; the input tile and its 1-pixel halo
 //                are staged in LDS 32 channels at a time, the K loop runs over 9 taps x 32 channels reading A fragments at
-//                tap offsets (no im2col buffer); weights are packed fragment-major with BatchNorm folded.  Epilogue: bias,
+//                tap offsets (no im2col buffer); weights are packed fragment-major (pack_fragments of og_conv_f32.h, shared with
+//                patchnet.hip) with BatchNorm folded.  Epilogue: bias,
 //                ReLU and, for conv{1,2,3}b, the 2x2 max-pool (floor semantics), so the unpooled map is never stored.
 //                convPa and convDa run as one launch with 512 output channels.
 //   cell         convPb (65) and convDb (D) on the 512-channel hidden map: softmax over 65, dustbin dropped, depth-to-space
 //                into the heatmap [B][Hc*8][Wc*8]; descriptor divided by its L2 norm (no eps) into [B][Hc][Wc][D].
 //   nms          kornia nms2d restated: replicate padding by (k-1)/2, a pixel is kept only when STRICTLY greater than the
 //                maximum of its k*k-1 neighbours (centre excluded); plus F.threshold (> thr, != 0) and remove_borders.
-//                Per (row, 256-column segment) counts, an exclusive scan per image, then compaction in raster order.
+//                Per (row, 256-column segment) counts, an exclusive scan per image, then compaction in raster order
+//                (block_exclusive_scan_inplace and block_rank_of of og_block.h).
 //   select       top_k_keypoints + min_stack on device: each candidate's rank under the key (score desc, raster index asc)
 //                is counted exactly, so the selection is identical from run to run and ties go to the lower raster index.
 //   describe     sample_desc_from_points (grid_sample bilinear, align_corners=False, zero padding) + F.normalize, LAFs, scores.
-#include "og_common.h"
+#include "og_block.h"
+#include "og_conv_f32.h"
 #include <cmath>
 
 namespace {
@@ -334,31 +337,7 @@ __global__ __launch_bounds__(256) void sp_nms_kernel(const float* __restrict__ h
 
 // exclusive scan of one image's segment counts (raster order), total -> counts[b]
 __global__ __launch_bounds__(256) void sp_scan_kernel(int32_t* __restrict__ seg, int nseg_img, int32_t* __restrict__ counts) {
-    __shared__ int32_t part[256];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    int32_t* sb = seg + (int64_t)b * nseg_img;
-    const int per = (nseg_img + 255) / 256;
-    const int lo = min(tid * per, nseg_img), hi = min(lo + per, nseg_img);
-    int sum = 0;
-    for (int i = lo; i < hi; ++i) sum += sb[i];
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        int run = 0;
-        for (int i = 0; i < 256; ++i) {
-            const int v = part[i];
-            part[i] = run;
-            run += v;
-        }
-        counts[b] = run;
-    }
-    __syncthreads();
-    int run = part[tid];
-    for (int i = lo; i < hi; ++i) {
-        const int v = sb[i];
-        sb[i] = run;
-        run += v;
-    }
+    block_exclusive_scan_inplace(seg + (int64_t)blockIdx.x * nseg_img, nseg_img, counts + blockIdx.x);
 }
 
 // candidates of one segment written at its scanned offset, in column order: cand_idx = y * Wh + x, cand_score = heat
@@ -368,16 +347,13 @@ __global__ __launch_bounds__(256) void sp_compact_kernel(const float* __restrict
     __shared__ int wsum[4];
     const int nseg = (Wh + SP_NMS_SEG - 1) / SP_NMS_SEG;
     const int s = blockIdx.x, y = blockIdx.y, b = blockIdx.z;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int x = s * SP_NMS_SEG + tid;
+    const int x = s * SP_NMS_SEG + (int)threadIdx.x;
     const int64_t pix = ((int64_t)b * Hh + y) * Wh + x;
     const bool keep = x < Wh && mask[pix];
-    const uint64_t bal = __ballot(keep);
-    if (lane == 0) wsum[wave] = __popcll(bal);
-    __syncthreads();
+    int cnt;
+    const int rank = block_rank_of(keep, wsum, cnt);
     if (!keep) return;
-    int off = seg[((int64_t)b * Hh + y) * nseg + s] + __popcll(bal & ((1ull << lane) - 1));
-    for (int w = 0; w < wave; ++w) off += wsum[w];
+    const int off = seg[((int64_t)b * Hh + y) * nseg + s] + rank;
     cidx[b * cap + off] = y * Wh + x;
     cscore[b * cap + off] = heat[pix];
 }
@@ -573,40 +549,21 @@ extern "C" int og_superpoint_pack(int32_t descriptor_dim, int32_t batch_norm, fl
     }
     // 3x3 convs, fragment-major; heads: convPa (conv 8) rows 0..255, convDa (conv 10) rows 256..511
     for (int l = 0; l < 8; ++l) {
-        const int Cin = kCin[l], Cout = kCout[l], nsteps = 9 * Cin / 8;
-        for (int co = 0; co < Cout; ++co) {
-            const int ci_conv = l < 7 ? l + 1 : (co < 256 ? 8 : 10);
-            const int row = l < 7 ? co : co % 256;
-            const float* w = params[2 * ci_conv];
-            const double sc = scale(ci_conv, row);
-            put(L.b[l] + co, shift(ci_conv, row));
-            for (int s = 0; s < nsteps; ++s) {
-                const int chunk = s / 36, tap = (s / 4) % 9, kk = s % 4;
-                for (int h = 0; h < 2; ++h)
-                    for (int e = 0; e < 4; ++e) {
-                        const int ci = chunk * 32 + kk * 8 + 4 * h + e;
-                        const int lanei = (co & 31) + 32 * h;
-                        put(L.w[l] + (((int64_t)(co / 32) * nsteps + s) * 64 + lanei) * 4 + e, (double)w[((int64_t)row * Cin + ci) * 9 + tap] * sc);
-                    }
-            }
-        }
+        const int Cin = kCin[l], Cout = kCout[l];
+        auto conv_of = [l](int co) { return l < 7 ? l + 1 : (co < 256 ? 8 : 10); };
+        for (int co = 0; co < Cout; ++co) put(L.b[l] + co, shift(conv_of(co), co % 256));
+        pack_fragments(put, L.w[l], Cout, Cout, 9 * Cin, [&](int co, int k) {
+            int ci, tap;
+            conv3x3_k(k, SP_KC, ci, tap);
+            return (double)params[2 * conv_of(co)][((int64_t)(co % 256) * Cin + ci) * 9 + tap] * scale(conv_of(co), co % 256);
+        });
     }
     // cell: tiles 0..2 convPb (conv 9, 65 rows, zero-padded to 96), tiles 3..10 convDb (conv 11)
-    for (int t = 0; t < SP_P_TILES + SP_D_TILES; ++t)
-        for (int j = 0; j < 32; ++j) {
-            const bool isP = t < SP_P_TILES;
-            const int row = (isP ? t : t - SP_P_TILES) * 32 + j;
-            const bool live = !isP || row < 65;
-            const int ic = isP ? 9 : 11;
-            const double sc = live ? scale(ic, row) : 0.0;
-            put(L.bc + (isP ? 0 : 32 * SP_P_TILES) + row, live ? shift(ic, row) : 0.0);
-            for (int s = 0; s < 32; ++s)
-                for (int h = 0; h < 2; ++h)
-                    for (int e = 0; e < 4; ++e) {
-                        const int ci = s * 8 + 4 * h + e;
-                        put(L.wc + (((int64_t)t * 32 + s) * 64 + j + 32 * h) * 4 + e, live ? (double)params[2 * ic][row * 256 + ci] * sc : 0.0);
-                    }
-        }
+    for (int row = 0; row < 32 * SP_P_TILES; ++row) put(L.bc + row, row < 65 ? shift(9, row) : 0.0);
+    for (int row = 0; row < SP_D; ++row) put(L.bc + 32 * SP_P_TILES + row, shift(11, row));
+    pack_fragments(put, L.wc, 65, 32 * SP_P_TILES, 256, [&](int row, int k) { return (double)params[18][row * 256 + k] * scale(9, row); });
+    pack_fragments(put, L.wc + (int64_t)SP_P_TILES * 32 * 256, SP_D, SP_D, 256,
+                   [&](int row, int k) { return (double)params[22][row * 256 + k] * scale(11, row); });
     return finite ? 0 : OG_E_RANGE;
 }
 

@@ -25,7 +25,7 @@
 //    backward: nll_grad_kernel writes the dense grad_scores the Sinkhorn backward takes; metric_scatter_kernel adds
 //    0.5 c (a^ - b^) for the O(M + N) distance entries that carry a gradient (float atomics: one row can be the hardest
 //    negative of many anchors); normalize_grad_kernel applies the Jacobian of the normalisation in place.
-#include "og_common.h"
+#include "og_block.h"
 
 namespace {
 
@@ -402,27 +402,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const float* __restrict__ d0,
     }
 }
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    // fixed-order: wave tree, then the 4 wave sums in wave order
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__device__ __forceinline__ int block_isum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[wave] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-// grid (B): per-pair terms of utils/losses.py -- every sum in a fixed order (thread-strided, then block_sum)
+// grid (B): per-pair terms of utils/losses.py -- every sum in a fixed order (thread-strided, then block_sum of og_block.h)
 __global__ __launch_bounds__(256) void pair_loss_kernel(const float* __restrict__ scores, const int64_t* __restrict__ gt0,
                                                         const int64_t* __restrict__ gt1, int m, int n, int margin_on, float margin, CritWs w) {
     __shared__ float red[4];
@@ -461,7 +441,7 @@ __global__ __launch_bounds__(256) void pair_loss_kernel(const float* __restrict_
             if (margin_on) h1 += fmaxf(margin - sv_unorderable((unsigned)(w.col[(int64_t)b * n + j] >> 32)), 0.f);
         }
     }
-    cm = block_isum(cm, ired); c0 = block_isum(c0, ired); c1 = block_isum(c1, ired);
+    cm = block_sum(cm, ired); c0 = block_sum(c0, ired); c1 = block_sum(c1, ired);
     sm = block_sum(sm, red); s0 = block_sum(s0, red); s1 = block_sum(s1, red);
     hm = block_sum(hm, red); h0 = block_sum(h0, red); h1 = block_sum(h1, red);
     if (threadIdx.x == 0) {

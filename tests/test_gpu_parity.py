@@ -671,6 +671,29 @@ def test_compact_matches(gpu_device):
     assert none["confidence"].numel() == 0
 
 
+@pytest.mark.parametrize("total", [1, 255, 256, 257, 65536, 65537])
+def test_compact_matches_scan_edges(gpu_device, total):
+    """B * M entries around the edges of the compaction: one partial workgroup, exactly one, two; 256 block counts (one per scan
+    thread) and 257 (two per thread, the last thread's range empty).  Against numpy's boolean-mask compaction, exactly."""
+    from openglue_amd import features
+    rng = np.random.default_rng(total)
+    B = 1 if total % 2 else 2
+    M, N = total // B, 37
+    m0 = rng.integers(0, N, (B, M))
+    m0[rng.random((B, M)) < 0.4] = -1
+    m0[0, 0] = m0[-1, -1] = 5                                    # the first and the last entry are matches
+    ms0 = rng.random((B, M), dtype=np.float32)
+    lafs0, lafs1 = rng.standard_normal((B, M, 2, 3), dtype=np.float32), rng.standard_normal((B, N, 2, 3), dtype=np.float32)
+    got = features.compact_matches(*(torch.from_numpy(a).to(gpu_device) for a in (m0, ms0, lafs0, lafs1)))
+    b, i = np.nonzero(m0 >= 0)
+    j = m0[b, i]
+    want = {"original_matching_idxs": np.stack([i, j], 1), "batch_indexes": b, "confidence": ms0[b, i], "lafs0": lafs0[b, i][None],
+            "lafs1": lafs1[b, j][None], "keypoints0": lafs0[b, i, :, 2], "keypoints1": lafs1[b, j, :, 2]}
+    assert set(got) == set(want)
+    for k in want:
+        assert np.array_equal(got[k].cpu().numpy(), want[k]), k
+
+
 def test_openglue_matcher_pipeline(gpu_device):
     """examples/openglue_matcher.py: OpenGlueMatcher (inference.py:83-209 with pre-extracted features): LAFs / responses / descriptors of
     two images -> compacted matches, against the same chain restated in the oracle (prepare_features_output -> SuperGlue.forward ->
