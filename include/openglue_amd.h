@@ -775,6 +775,70 @@ int og_warp_perspective_u8(int32_t batch, int32_t H, int32_t W, int32_t C, const
 int og_homography_pairs(int32_t batch, int32_t H, int32_t W, int32_t C, const uint8_t* frames, int32_t offset, const float* warp_offset,
                         float* image0, float* image1, float* H_true, void* workspace_dev, void* stream);
 
+/* ABI v14, additive -- MegaDepth training pairs (csrc/megadepth.hip): the arithmetic of the reference's main-stage data items,
+ * MegaDepthPairsDataset.__getitem__ (data/megadepth_dataset.py:119-192), MegaDepthPairsDatasetFeatures.__getitem__ (:203-282) and the collate
+ * stack_keypoints_batch (data/megadepth_datamodule.py:105-166): grey, cv2.resize of the image and of its depth map, crop, K; for cached
+ * features the crop mask, the selection of num_keypoints keypoints and one depth value per keypoint.  Device pointers only (the tables also
+ * in a host copy, which is what gets validated), no host synchronisation, no allocation; every result is bit-identical from run to run and
+ * independent of the batch it is computed in.  tests/megadepth_ref.py is the specification.  Limits: every image side and resized side in
+ * [1, 32768], at most 65535 images per call, C in {1, 3}; anything else returns OG_E_SHAPE, a null pointer OG_E_INVALID, an unknown
+ * interpolation OG_E_FLAG, a float output that is not 16-byte aligned (or a float input not 4-byte aligned) OG_E_ALIGN -- all before
+ * anything is launched.
+ *
+ * The resize of an axis from src to dst: scale = 1.0 / ((double)dst / src); destination index d has f = (float)((d + 0.5) scale - 0.5),
+ * s = floor(f), f -= s; s < 0 -> s = 0, f = 0; s >= src - 1 -> s = src - 1, f = 0; taps s and min(s + 1, src - 1).
+ * og_resize_linear_u8: src [batch][H][W][C] bytes -> dst [batch][h][w][C], the window with origin (x0, y0) and size w x h of the images
+ *   resized to dw x dh as cv2.resize(INTER_LINEAR) does on bytes: coefficients rint((1 - f) 2048) and rint(f 2048) (half to even),
+ *   R = S[s] a0 + S[s + 1] a1 along x in int32, out = (((b0 (R0 >> 4)) >> 16) + ((b1 (R1 >> 4)) >> 16) + 2) >> 2 along y.
+ * og_resize_f32: src [batch][H][W] float -> dst [batch][h][w].  nearest = 0: the same taps with the float coefficients 1 - f and f,
+ *   S[s] a0 + S[s + 1] a1 then R0 b0 + R1 b1, products and sums rounded separately; nearest = 1: s = min(floor(d scale), src - 1) in double.
+ * og_megadepth_pairs: `frames` table entries (both images of every pair), each resized to resize_w x resize_h and cut to the tw x th window
+ *   at (x0, y0) -> images [frames][th][tw] = resize_linear_u8(grey(image)) / 255.f with grey(R, G, B) = (9798 R + 19235 G + 3735 B + 16384)
+ *   >> 15 taken on the source taps (C = 1: the byte), depths [frames][th][tw] = resize_f32(depth), K_out [frames][3][3] =
+ *   diag((float)((double)resize_w / W), (float)((double)resize_h / H), 1) K in float, then K[0][2] -= x0, K[1][2] -= y0.  Two launches;
+ *   neither the grey image nor a whole resized image or map is written anywhere.
+ * og_megadepth_features: `images` table entries -> lafs [images][k][2][3], scores [images][k], descriptors [images][k][desc_dim], depth
+ *   [images][k], K_out [images][3][3] with k = num_keypoints <= 4096, n <= 8192 keypoints per image.  Keypoints with start <= c < start +
+ *   target on the cropped axis survive (c = lafs[i][axis][2]; axis -1: all) and are shifted by start.  At most k survivors: in their
+ *   order, zero padded.  More: the k largest keys (keys, or the scores when keys is NULL) in descending order, the lower index first on
+ *   ties.  depth = depth_map[ny(int(y') + start_y)][nx(int(x') + start_x)] through the nearest index maps from image_w x image_h to the
+ *   map's own size, 0 for a keypoint outside the cropped image.  K as above with orig -> image and the shift on the cropped axis only.
+ *   One launch, one workgroup per image. */
+typedef struct og_md_frame {
+    const uint8_t* image;         /* [H][W][C] */
+    const float* depth;           /* [H][W] */
+    const float* K;               /* [3][3] */
+    int32_t H, W, C;
+    int32_t resize_w, resize_h;
+    int32_t x0, y0;               /* origin of the crop in the resized image */
+    int32_t reserved;
+} og_md_frame;
+
+typedef struct og_md_features {
+    const float* lafs;            /* [n][2][3] */
+    const float* scores;          /* [n] */
+    const float* descriptors;     /* [n][desc_dim] */
+    const float* keys;            /* [n] or NULL: what the selection ranks */
+    const float* depth;           /* [depth_h][depth_w] */
+    const float* K;               /* [3][3] */
+    int32_t n;
+    int32_t image_w, image_h;     /* the size the features were extracted at */
+    int32_t orig_w, orig_h;       /* the size K refers to */
+    int32_t depth_w, depth_h;
+    int32_t axis, start;          /* crop: axis 0 = x, 1 = y, -1 = none (start 0) */
+    int32_t reserved;
+} og_md_features;
+
+int og_resize_linear_u8(int32_t batch, int32_t H, int32_t W, int32_t C, const uint8_t* src, int32_t dw, int32_t dh, int32_t x0, int32_t y0,
+                        int32_t w, int32_t h, uint8_t* dst, void* stream);
+int og_resize_f32(int32_t batch, int32_t H, int32_t W, const float* src, int32_t dw, int32_t dh, int32_t nearest, int32_t x0, int32_t y0,
+                  int32_t w, int32_t h, float* dst, void* stream);
+int og_megadepth_pairs(int32_t frames, int32_t tw, int32_t th, const og_md_frame* table_host, const og_md_frame* table_dev, float* images,
+                       float* depths, float* K_out, int32_t depth_nearest, void* stream);
+int og_megadepth_features(int32_t images, int32_t tw, int32_t th, int32_t num_keypoints, int32_t desc_dim, const og_md_features* table_host,
+                          const og_md_features* table_dev, float* lafs, float* scores, float* descriptors, float* depth, float* K_out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

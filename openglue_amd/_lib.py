@@ -84,6 +84,16 @@ class og_adam_layout_t(C.Structure):
                 ("num_partials", C.c_int32), ("chunk", C.c_int32), ("reserved", C.c_int32)]
 
 
+class og_md_frame(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("depth", C.c_void_p), ("K", C.c_void_p)] + \
+               [(k, C.c_int32) for k in ("H", "W", "C", "resize_w", "resize_h", "x0", "y0", "reserved")]
+
+
+class og_md_features(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("lafs", "scores", "descriptors", "keys", "depth", "K")] + \
+               [(k, C.c_int32) for k in ("n", "image_w", "image_h", "orig_w", "orig_h", "depth_w", "depth_h", "axis", "start", "reserved")]
+
+
 # every symbol include/openglue_amd.h declares: name -> (restype, argtypes)
 _i32, _i64, _f, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
 SYMBOLS = {
@@ -197,6 +207,10 @@ SYMBOLS = {
     "og_perspective_transform": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
     "og_warp_perspective_u8": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "og_homography_pairs": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_resize_linear_u8": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "og_resize_f32": (C.c_int, [_i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "og_megadepth_pairs": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
+    "og_megadepth_features": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
