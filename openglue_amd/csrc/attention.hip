@@ -69,7 +69,7 @@ constexpr float SUM_LIMIT = OG_ATTN_SUMLIMIT;         // attention_dma_kernel: t
 #ifndef OG_ATTN_DBG
 #define OG_ATTN_DBG 0      // debugging: 1 = P split in C++ instead of the 3-instruction asm
 #endif
-#if OG_ATTN_TRACE
+#if OG_ATTN_TRACE & 1
 __device__ unsigned og_attn_trace_buf[2][4][16][8];
 #define OG_TP(i)                                                                                         \
     do {                                                                                                 \
@@ -79,6 +79,26 @@ __device__ unsigned og_attn_trace_buf[2][4][16][8];
     } while (0)
 #else
 #define OG_TP(i) do {} while (0)
+#endif
+// -DOG_ATTN_TRACE=2 (scripts/trace_attention_tail.py): five stamps over the LIFE of every wave of attention_dma_kernel's first OG_LIFE_WG workgroups -- 0 entry,
+// 1 in front of tile 0's step (Q, K(0), V(0) landed, the barrier passed), 2 behind the last tile's step, 3 the last O store issued, 4 the stores complete -- read
+// back by og_debug_attn_life().  The stamp is one asm statement with its own lgkmcnt(0) and stands outside the tile steps, whose LDS waits are counted by hand.
+#ifndef OG_ATTN_TAIL8
+#define OG_ATTN_TAIL8 0       // experiment: 1 = the store tail keeps its 8-byte stores whatever ldo is (the tail before the half-wave exchange)
+#endif
+#if OG_ATTN_TRACE & 2
+constexpr int OG_LIFE_WG = 2048;
+__device__ unsigned og_attn_life_buf[OG_LIFE_WG][4][5];
+#define OG_LIFE(i)                                                                                       \
+    do {                                                                                                 \
+        unsigned long long t_;                                                                           \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory");                     \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        life[i] = (unsigned)t_;                                                                          \
+    } while (0)
+#else
+#define OG_LIFE(i) do {} while (0)
 #endif
 
 
@@ -112,6 +132,69 @@ __device__ __forceinline__ void lds_read_tr8_b64(i32x2& d, unsigned addr) {
 // pipelined loop: K fragment read order -- pieces 0, 1 = hi of key blocks 0, 1 (double-buffered by chunk), 2, 3 = lo (ONE buffer: the pass-0 MFMAs alone read it)
 // -> read_k1's piece index (key block j >> 1, plane j & 1)
 __device__ constexpr int og_korder(int q) { return q == 0 ? 0 : q == 1 ? 2 : q == 2 ? 1 : 3; }
+
+// The store tail of the three forward kernels: O = acc * inv as (hi, lo) f16 planes, one query row per lane.  A lane holds NG groups of four consecutive
+// channels of its row: val(g, e) is accumulator e of group g, whose first channel is c0 + CSTEP g + clane (c0 = the head's first output column).
+// PAIR32 (the 32x32 MFMA layout: CSTEP = 8, clane = 4 hi, lanes l and l + 32 own the same query): lanes l and l + 32 hold the two 8-byte halves of one aligned
+// 16-byte run, so as 8-byte stores the tail is 2 NG store instructions per lane and is bound by their ISSUE, not by bandwidth.  v_permlane32_swap exchanges
+// lanes 32-63 of its first operand with lanes 0-31 of its second: with (first, second) = the dwords of groups (g, g + 1), g even, lanes 0-31 end up with the
+// eight channels of slot g = [own g | partner's g] and lanes 32-63 with those of slot g + 1 = [partner's g + 1 | own g + 1] -- ONE 16-byte store per pair and
+// plane, the same bytes at the same addresses (both planes keep eight aligned channels contiguous in the plain and in the hl32 layout).  The swaps stand in front
+// of the row predicate so that every lane takes part (the predicate is the same for l and l + 32), on distinct registers, as the builtin: the
+// compiler places the wait states between the conversion that writes an operand and the swap.  The 16-byte stores need ldo to be a multiple of 8 halves;
+// og_launch_attention accepts multiples of 4, which keep the 8-byte stores (wave-uniform choice).
+typedef unsigned og_u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned og_u32x4 __attribute__((ext_vector_type(4)));
+template <int NG, int CSTEP, bool PAIR32, class V>
+__device__ __forceinline__ void og_attn_store_o(const AttnArgs& a, int64_t orow, int c0, int clane, int hi, float inv, bool live, V&& val) {
+    og_u32x2 ph[NG], pl[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        f16x4 vh, vl;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float o = val(g, e) * inv;
+            asm("" : "+v"(o));          // one materialised product for both halves of og_split (og_common.h)
+            _Float16 th, tl;
+            og_split(o, th, tl);
+            vh[e] = th; vl[e] = tl;
+        }
+        ph[g] = __builtin_bit_cast(og_u32x2, vh);
+        pl[g] = __builtin_bit_cast(og_u32x2, vl);
+    }
+    auto at = [&](int c) { return orow + (a.o_hl ? og_hl_col(c) : (int64_t)c); };
+    if constexpr (PAIR32) {
+        static_assert(CSTEP == 8 && NG % 2 == 0, "pairs of 8-channel slots");
+        if (!OG_ATTN_TAIL8 && (a.ldo & 7) == 0) {
+#pragma unroll
+            for (int g = 0; g < NG; g += 2)
+#pragma unroll
+                for (int w = 0; w < 2; ++w) {
+                    const auto rh = __builtin_amdgcn_permlane32_swap(ph[g][w], ph[g + 1][w], false, false);
+                    ph[g][w] = rh[0]; ph[g + 1][w] = rh[1];
+                    const auto rl = __builtin_amdgcn_permlane32_swap(pl[g][w], pl[g + 1][w], false, false);
+                    pl[g][w] = rl[0]; pl[g + 1][w] = rl[1];
+                }
+            if (live) {
+#pragma unroll
+                for (int g = 0; g < NG; g += 2) {
+                    const int64_t oo = at(c0 + 8 * (g + hi));
+                    *reinterpret_cast<og_u32x4*>(a.oh + oo) = og_u32x4{ph[g][0], ph[g][1], ph[g + 1][0], ph[g + 1][1]};
+                    *reinterpret_cast<og_u32x4*>(a.ol + oo) = og_u32x4{pl[g][0], pl[g][1], pl[g + 1][0], pl[g + 1][1]};
+                }
+            }
+            return;
+        }
+    }
+    if (live) {
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const int64_t oo = at(c0 + CSTEP * g + clane);
+            *reinterpret_cast<og_u32x2*>(a.oh + oo) = ph[g];
+            *reinterpret_cast<og_u32x2*>(a.ol + oo) = pl[g];
+        }
+    }
+}
 
 template <int DH, class RD>
 __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attention_kernel(AttnArgs a, RD rd) {      // dh = 128 (round 6: two heads at 256-d): 136 KB of LDS, one workgroup per CU
@@ -292,7 +375,7 @@ __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attention_kernel(AttnArg
             }
     };
     const int ntiles = (nk + KV_TILE - 1) / KV_TILE;
-#if OG_ATTN_TRACE
+#if OG_ATTN_TRACE & 1
     const int tsel = blockIdx.x == 8 * 40 ? 0 : blockIdx.x == 8 * 41 + 3 ? 1 : -1;     // two workgroups somewhere in the middle
     unsigned tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -411,7 +494,7 @@ __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attention_kernel(AttnArg
             __syncthreads();
         }
         OG_TP(7);
-#if OG_ATTN_TRACE
+#if OG_ATTN_TRACE & 1
         if (tsel >= 0 && lane == 0 && kt < 16)
 #pragma unroll
             for (int i = 0; i < 8; ++i) og_attn_trace_buf[tsel][wave][kt][i] = tp[i];
@@ -431,29 +514,8 @@ __global__ __launch_bounds__(256, DH > 64 ? 1 : 2) void attention_kernel(AttnArg
     // row log-sum-exp of the (scaled) scores in natural units, for a backward pass that recomputes P (uniform calls only):
     // the kernel works in base 2 (q carries log2 e): L = ln 2 (m_run + log2 l)
     if (a.lse && hi == 0 && qi < nq) a.lse[((int64_t)z * a.num_heads + h) * nq + qi] = (m_run + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-    if (qi < nq) {
-        const int64_t orow = (q_row0 + qi) * a.ldo;
-#pragma unroll
-        for (int d = 0; d < NDV; ++d)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int dv = d * 32 + 8 * g4 + 4 * hi;
-                if (dv < DH) {
-                    f16x4 vh, vl;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float o = oacc[d][4 * g4 + e] * inv;
-                        asm("" : "+v"(o));          // one materialised product for both halves of og_split (og_common.h)
-                        _Float16 th, tl;
-                        og_split(o, th, tl);
-                        vh[e] = th; vl[e] = tl;
-                    }
-                    const int64_t oo = orow + (a.o_hl ? og_hl_col(h * DH + dv) : (int64_t)(h * DH + dv));
-                    *reinterpret_cast<f16x4*>(a.oh + oo) = vh;
-                    *reinterpret_cast<f16x4*>(a.ol + oo) = vl;
-                }
-            }
-    }
+    // group g = channels 8 g + 4 hi ..: accumulator block g >> 2, registers 4 (g & 3) ..; dh = 16 uses the first two groups of its padded block
+    og_attn_store_o<DH / 8, 8, true>(a, (q_row0 + qi) * a.ldo, h * DH, 4 * hi, hi, inv, qi < nq, [&](int g, int e) { return oacc[g >> 2][4 * (g & 3) + e]; });
 }
 
 
@@ -568,6 +630,10 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
     if (((id >> 3) >> (OG_ATTN_PRIO - 1)) & 1) __builtin_amdgcn_s_setprio(1);
 #endif
 
+#if OG_ATTN_TRACE & 2
+    unsigned life[5] = {0, 0, 0, 0, 0};
+#endif
+    OG_LIFE(0);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave_all = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = KS == 2 ? wave_all >> 2 : 0;        // which half of the key range
@@ -796,7 +862,7 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
     [[maybe_unused]] int mx_sa = a.mx_scale_a;            // E8M0 bytes of the A-side block scale: 127 + sv - 11 (byte 0)
     asm volatile("" : "+v"(mx_sa));
 
-#if OG_ATTN_TRACE
+#if OG_ATTN_TRACE & 1
     const int tsel = blockIdx.x == 8 * 40 ? 0 : blockIdx.x == 8 * 41 + 3 ? 1 : -1;     // two workgroups somewhere in the middle
     unsigned tp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -1096,7 +1162,7 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
             __syncthreads();                                      // ... everybody's did, and everybody is done with tile t
         }
         OG_TP(6);
-#if OG_ATTN_TRACE
+#if OG_ATTN_TRACE & 1
         tp[7] = tp[6];
         if (tsel >= 0 && lane == 0 && kt < 16)
 #pragma unroll
@@ -1427,6 +1493,7 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
         using B0 = std::integral_constant<int, 0>; using B1 = std::integral_constant<int, 1>;
         using F0 = std::integral_constant<int, 0>; using F1 = std::integral_constant<int, 1>; using FR = std::integral_constant<int, -1>;
         using Y = std::true_type; using N = std::false_type;
+        OG_LIFE(1);
         tile_step(0, B0{}, Y{}, FR{}, Y{}, ntiles == 1 ? 0 : ntiles == 2 ? 2 : 1);
         int kt = 1;
         for (; kt + 3 < ntiles; kt += 2) {
@@ -1438,6 +1505,7 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
         if (left == 3) { tile_step(kt, B0{}, N{}, FR{}, N{}, 2); ++kt; }
         if (left == 2) tile_step(kt, B0{}, Y{}, F0{}, N{}, 0);
         else if (left & 1) tile_step(kt, B1{}, Y{}, F0{}, N{}, 0);
+        OG_LIFE(2);
     }
 
     if constexpr (KS == 2) {
@@ -1539,27 +1607,15 @@ __global__ __launch_bounds__(PIPE == 2 ? 512 : 256 * KS, PIPE == 2 ? 2 : KS == 2
     // row log-sum-exp of the (scaled) scores in natural units, for a backward pass that recomputes P (uniform calls only):
     // the kernel works in base 2 (q carries log2 e): L = ln 2 (m_run + log2 l)
     if (a.lse && hi == 0 && qi < nq) a.lse[((int64_t)z * a.num_heads + h) * nq + qi] = (m_run + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-    if (qi < nq) {
-        const int64_t orow = (q_row0 + qi) * a.ldo;
+    og_attn_store_o<DH / 8, 8, true>(a, (q_row0 + qi) * a.ldo, h * DH, 4 * hi, hi, inv, qi < nq, [&](int g, int e) { return oacc[g >> 2][4 * (g & 3) + e]; });
+#if OG_ATTN_TRACE & 2
+    OG_LIFE(3);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    OG_LIFE(4);
+    if (lane == 0 && blockIdx.x < OG_LIFE_WG)
 #pragma unroll
-        for (int d = 0; d < NDV; ++d)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4) {
-                const int dv = d * 32 + 8 * g4 + 4 * hi;
-                f16x4 vh, vl;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float o = oacc[d][4 * g4 + e] * inv;
-                    asm("" : "+v"(o));          // one materialised product for both halves of og_split (og_common.h)
-                    _Float16 th, tl;
-                    og_split(o, th, tl);
-                    vh[e] = th; vl[e] = tl;
-                }
-                const int64_t oo = orow + (a.o_hl ? og_hl_col(h * DH + dv) : (int64_t)(h * DH + dv));
-                *reinterpret_cast<f16x4*>(a.oh + oo) = vh;
-                *reinterpret_cast<f16x4*>(a.ol + oo) = vl;
-            }
-    }
+        for (int i = 0; i < 5; ++i) og_attn_life_buf[blockIdx.x][wave][i] = life[i];
+#endif
 }
 
 
@@ -1981,25 +2037,8 @@ __global__ __launch_bounds__(256, 2) void attention_p16_kernel(AttnArgs a, RD rd
         const float inv = 1.f / l_tot;
         const int qi = q0 + wave * 32 + 16 * j + c16;
         if (a.lse && g == 0 && qi < nq) a.lse[((int64_t)z * a.num_heads + h) * nq + qi] = (m_run[j] + __builtin_amdgcn_logf(l_tot)) * 0.6931471805599453f;
-        if (qi < nq) {
-            const int64_t orow = (q_row0 + qi) * a.ldo;
-#pragma unroll
-            for (int tt = 0; tt < 4; ++tt) {
-                const int dv = 16 * tt + 4 * g;
-                f16x4 vh, vl;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    float o = oacc[tt][j][e] * inv;
-                    asm("" : "+v"(o));
-                    _Float16 th, tl;
-                    og_split(o, th, tl);
-                    vh[e] = th; vl[e] = tl;
-                }
-                const int64_t oo = orow + (a.o_hl ? og_hl_col(h * DH + dv) : (int64_t)(h * DH + dv));
-                *reinterpret_cast<f16x4*>(a.oh + oo) = vh;
-                *reinterpret_cast<f16x4*>(a.ol + oo) = vl;
-            }
-        }
+        // 8-byte stores: the halves of a 16-byte run sit in lanes l and l + 16 here, which v_permlane32_swap does not exchange
+        og_attn_store_o<4, 16, false>(a, (q_row0 + qi) * a.ldo, h * DH, 4 * g, 0, inv, qi < nq, [&](int tt, int e) { return oacc[tt][j][e]; });
     }
 }
 
@@ -2160,10 +2199,16 @@ int og_launch_attention(const AttnArgs& a, hipStream_t stream) {
     return og_launch_status();
 }
 
-#if OG_ATTN_TRACE
+#if OG_ATTN_TRACE & 1
 extern "C" int og_debug_attn_trace(void* host_dst, size_t bytes) {
     if (bytes > sizeof(og_attn_trace_buf)) bytes = sizeof(og_attn_trace_buf);
     return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(og_attn_trace_buf), bytes);
+}
+#endif
+#if OG_ATTN_TRACE & 2
+extern "C" int og_debug_attn_life(void* host_dst, size_t bytes) {
+    if (bytes > sizeof(og_attn_life_buf)) bytes = sizeof(og_attn_life_buf);
+    return (int)hipMemcpyFromSymbol(host_dst, HIP_SYMBOL(og_attn_life_buf), bytes);
 }
 #endif
 
