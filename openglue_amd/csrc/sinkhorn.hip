@@ -394,6 +394,10 @@ __global__ __launch_bounds__(256) void sinkhorn_sweep_fast_kernel(const float* _
     float* ub = u + (int64_t)b * ldu;
     const float dcol2 = zr2 + vb[N] * in_scale;  // dustbin column entry of every row (without u)
     const float la2 = la * LOG2E;
+    // Rows >= M of the last workgroup have p = 0 whatever their u, and their row sum is the dustbin term alone.  Their u is chosen so
+    // that this term is 1: with u = 0 and (z / reg + v_N) below -150 bits it underflowed to 0, log2 gave -inf, f = exp2(+inf) = inf and
+    // 0 * inf = NaN entered every column sum of the stream.
+    const float u_pad = -dcol2 * (in_scale == 1.f ? 1.f : LN2);      // u is multiplied by in_scale (1 or log2 e) where it is used
 
     float vv[CPL][4], cs[CPL][4];
 #pragma unroll
@@ -414,7 +418,7 @@ __global__ __launch_bounds__(256) void sinkhorn_sweep_fast_kernel(const float* _
         for (int r = 0; r < RG; ++r) {
             const int row = row0 + r;
             const float* sp = S + (int64_t)row * lds;
-            nu[r] = row < M ? ub[row] : 0.f;
+            nu[r] = row < M ? ub[row] : u_pad;
 #pragma unroll
             for (int k = 0; k < CPL; ++k) {
                 const int c0 = cbase + 256 * k;

@@ -1,5 +1,5 @@
 """Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py, tests/test_gpu_gemm_forms.py, tests/test_gpu_proj_mlp_forms.py,
-tests/test_gpu_attention_backward.py) and the form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
+tests/test_gpu_attention_backward.py, tests/test_gpu_sinkhorn_forms.py) and the form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
 their own.
 
 launched_kernels(fn) runs fn() under torch.profiler (ProfilerActivity.CUDA: on ROCm, kineto's roctracer records every dispatched kernel
@@ -16,6 +16,8 @@ ATTENTION_FORWARD = ("attention_kernel<", "attention_dma_kernel<", "attention_p1
 GEMM = ("gemm_nt_f32_kernel<", "gemm_nt_f16x3_kernel<", "gemm_nt_f16x3_big_kernel<", "gemm_nt_f16x3_big2_kernel<")
 PROJ_MLP = ("mlp_small_kernel<", "mlp_fused_kernel<", "proj_small_kernel<", "proj_stream_kernel<")
 ATTENTION_TRAIN = ("attention_bwd_kernel<", "attention_lse_kernel<", "attention_delta_kernel")     # csrc/attention_train.hip
+SINKHORN = ("sinkhorn_sweep_kernel<", "sinkhorn_sweep_fast_kernel<", "sinkhorn_combine_kernel<", "sinkhorn_combine_fast_kernel<", "sinkhorn_scores_kernel<",
+            "sinkhorn_resident_kernel<", "sinkhorn_fallback_kernel<")     # csrc/sinkhorn.hip, csrc/sinkhorn_resident.hip: the inference Sinkhorn
 PROJ_WSTAT = "proj_wstat_kernel"       # csrc/proj_wstat.hip: the weight-stationary q | k | v projection of 256-d batches (no template arguments)
 
 
@@ -77,3 +79,8 @@ def proj_mlp_instances(names) -> list:
 def attention_train_instances(names) -> list:
     """The softmax-attention training launches (csrc/attention_train.hip: backward, row log-sum-exp, delta) among `names`, in launch order."""
     return [n for n in names if n.startswith(ATTENTION_TRAIN)]
+
+
+def sinkhorn_instances(names) -> list:
+    """The inference-Sinkhorn launches (csrc/sinkhorn.hip, csrc/sinkhorn_resident.hip) among `names`, in launch order, one entry per launch."""
+    return [n for n in names if n.startswith(SINKHORN)]
