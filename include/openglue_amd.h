@@ -618,6 +618,40 @@ int og_superpoint_detect(int32_t batch, int32_t Hh, int32_t Wh, int32_t nms_kern
 int og_superpoint_describe(int32_t batch, int32_t Hc, int32_t Wc, int32_t n, const int32_t* sel_idx, const float* sel_score,
                            int64_t sel_ld, const float* coarse_desc, float* lafs, float* scores, float* descriptors, void* stream);
 
+/* Fine-tuning SuperPointNet (no BatchNorm, descriptor_dim 256): the training forward and the backward of the extractor
+ * (csrc/superpoint_train.hip; models/matching_module.py `finetune: True`).  Exact fp32, no atomics: gradients are bit-identical from
+ * run to run.  Additive to ABI v14.
+ *
+ * og_superpoint_train_forward: og_superpoint_dense (same packed blob, same heatmap and coarse descriptors bit for bit) that keeps
+ *   the post-ReLU output of every 3x3 layer in `saved` (og_superpoint_train_saved_bytes, 16-byte aligned).  `saved` begins with the
+ *   hidden map of the two heads, [B Hc Wc][512] (convPa | convDa after ReLU).
+ * og_superpoint_train_pack (host): params as og_superpoint_pack (24 pointers) -> the data-gradient blob,
+ *   og_superpoint_train_packed_bytes bytes: for layer j = conv1b, 2a, 2b, 3a, 3b, 4a, 4b, heads (convPa | convDa as one layer of 512
+ *   output channels) in this order a block of Cout * 9 * Cin floats, the weights transposed and the taps flipped in the fragment-major
+ *   layout of the forward blob: [ci / 32][step][lane][4], step = ((co / 32) * 9 + tap') * 4 + kk, lane l element e holding
+ *   W[co = 32 (co / 32) + 8 kk + 4 (l >> 5) + e][ci = 32 (ci / 32) + (l & 31)][tap = 8 - tap'].
+ * og_superpoint_train_backward: g_hidden [B Hc Wc][512] = the gradient of the heads' hidden map BEFORE its ReLU ->  `grads`, flat:
+ *   conv1a weight [64][9], bias [64], then per layer j weight [Cout][Cin][9] (torch's order) and bias [Cout]; heads rows 0..255 are
+ *   convPa, 256..511 convDa.  first_layer: 0 = conv1a, 1 + j = layer j; layers below it are neither computed nor written.
+ *   layer_grads (debug, may be NULL): receives, for every layer j visited, the gradient of its pre-activation output at the layer's
+ *   own resolution as the kernels form it (pool routing applied), [B][h_j][w_j][Cout_j] one after the other for j = 0..7.
+ *   Workspace og_superpoint_train_workspace_bytes(batch, H, W, n), 16-byte aligned, shared with og_superpoint_describe_backward.
+ * og_superpoint_describe_backward: d_descriptors [B][n][256] -> d_coarse [B][Hc][Wc][256], the gradient of the coarse (normalised)
+ *   descriptors through F.normalize and the bilinear sampling; each cell gathers from the keypoints that touch it, in keypoint order.
+ *   n >= 1. */
+size_t og_superpoint_train_packed_bytes(int32_t descriptor_dim);
+int og_superpoint_train_pack(int32_t descriptor_dim, const float* const* params, void* packed_host);
+size_t og_superpoint_train_saved_bytes(int32_t batch, int32_t H, int32_t W);
+size_t og_superpoint_train_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t n);
+int og_superpoint_train_forward(int32_t batch, int32_t H, int32_t W, const float* image, const void* packed_dev, void* saved_dev,
+                                float* heatmap, float* coarse_desc, void* stream);
+int og_superpoint_train_backward(int32_t batch, int32_t H, int32_t W, const float* image, const void* packed_grad_dev,
+                                 const void* saved_dev, const float* g_hidden, int32_t first_layer, float* grads, float* layer_grads,
+                                 void* workspace_dev, void* stream);
+int og_superpoint_describe_backward(int32_t batch, int32_t Hc, int32_t Wc, int32_t n, const int32_t* sel_idx, int64_t sel_ld,
+                                    const float* coarse_desc, const float* d_descriptors, float* d_coarse, void* workspace_dev,
+                                    void* stream);
+
 /* ABI v14 -- the reference's optimizer step: torch.optim.Adam + StepLR(step_size=1) stepped every iteration (models/matching_module.py:133-147)
  * behind torch.nn.utils.clip_grad_norm_ (train.py:73 gradient_clip_val), fused into three launches whatever the number of parameters
  * (csrc/optimizer.hip).  The caller owns three flat fp32 device buffers grad / exp_avg / exp_avg_sq of layout.total floats in which

@@ -29,18 +29,50 @@ def _method(method: str):
         raise NameError("Unexpected name for the method: {}".format(method))      # laf_converter.py:128
 
 
-def prepare_features_output(lafs: torch.Tensor, responses: torch.Tensor, desc: torch.Tensor, method: str = "none",
-                            permute_desc: bool = False, log_response: bool = False) -> Dict[str, torch.Tensor]:
-    """lafs [B,N,2,3], responses [B,N], desc [B,N,D] -> {'keypoints' [B,N,2], 'side_info' [B,N,s], 'local_descriptors'}."""
-    code, s = _method(method)
-    lafs, responses = _lib.gpu_tensor(lafs, "lafs", convert=True), _lib.gpu_tensor(responses, "responses", convert=True)
+def _prepare(lafs: torch.Tensor, responses: torch.Tensor, code: int, s: int, log_response: bool):
     B, N = responses.shape
-    if lafs.shape != (B, N, 2, 3):
-        raise ValueError("lafs must be [B, N, 2, 3]")
     kpts = torch.empty(B, N, 2, device=lafs.device, dtype=torch.float32)
     side = torch.empty(B, N, s, device=lafs.device, dtype=torch.float32)
     _lib.call("og_prepare_features", lafs.device, lafs.data_ptr(), responses.data_ptr(), B * N, code, int(log_response), kpts.data_ptr(),
               side.data_ptr(), _lib.STREAM)
+    return kpts, side
+
+
+class _PrepareFeatures(torch.autograd.Function):
+    """og_prepare_features with the gradient of the response column of side_info: 1, or 1 / (response + 0.1) under log_response.
+    The LAF columns and the keypoints carry none (keypoint positions are integers upstream)."""
+
+    @staticmethod
+    def forward(ctx, lafs, responses, code, s, log_response):
+        kpts, side = _prepare(lafs, responses, code, s, log_response)
+        ctx.log_response = log_response
+        ctx.save_for_backward(responses)
+        ctx.mark_non_differentiable(kpts)
+        return kpts, side
+
+    @staticmethod
+    def backward(ctx, _dkpts, dside):
+        (responses,) = ctx.saved_tensors
+        g = dside[..., 0]
+        return None, (g / (responses + 0.1) if ctx.log_response else g.clone()), None, None, None
+
+
+def prepare_features_output(lafs: torch.Tensor, responses: torch.Tensor, desc: torch.Tensor, method: str = "none",
+                            permute_desc: bool = False, log_response: bool = False) -> Dict[str, torch.Tensor]:
+    """lafs [B,N,2,3], responses [B,N], desc [B,N,D] -> {'keypoints' [B,N,2], 'side_info' [B,N,s], 'local_descriptors'}.
+    When `responses` requires grad (a fine-tuned extractor) the response column of side_info carries it."""
+    code, s = _method(method)
+    differentiable = isinstance(responses, torch.Tensor) and responses.requires_grad and torch.is_grad_enabled()
+    if differentiable:
+        if not responses.is_cuda or responses.dtype != torch.float32:
+            raise RuntimeError("responses: expected a float32 tensor on the GPU; openglue_amd has no CPU path")
+        lafs, resp = _lib.gpu_tensor(lafs, "lafs", convert=True), responses.contiguous()
+    else:
+        lafs, resp = _lib.gpu_tensor(lafs, "lafs", convert=True), _lib.gpu_tensor(responses, "responses", convert=True)
+    B, N = resp.shape
+    if lafs.shape != (B, N, 2, 3):
+        raise ValueError("lafs must be [B, N, 2, 3]")
+    kpts, side = _PrepareFeatures.apply(lafs, resp, code, s, log_response) if differentiable else _prepare(lafs, resp, code, s, log_response)
     return {"keypoints": kpts, "side_info": side, "local_descriptors": desc.permute(0, 2, 1) if permute_desc else desc}
 
 

@@ -1,5 +1,5 @@
 """SuperPoint detector and descriptor on HIP kernels: drop-ins for SuperPointNet / SuperPointNetBn of the reference
-(models/features/superpoint/model.py), inference only.
+(models/features/superpoint/model.py).  Inference for both; SuperPointNet is also differentiable (the reference's `finetune: True`).
 
 Same constructor arguments and defaults, same state-dict keys and shapes, same `weights=` loading, and `forward(image, mask=None)`
 returns (lafs [B, N, 2, 3], scores [B, N], descriptors [B, N, 256]) -- what features.prepare_features_output and
@@ -12,6 +12,11 @@ Semantics reproduced: the trunk and heads of model.py (BatchNorm folded into the
 equal scores undefined (torch.topk), equal scores are ordered by raster index, lower first.
 
 One device -> host synchronisation per call: the kept count, which sizes the outputs.
+
+Fine-tuning: SuperPointNet.forward in train() mode, with grad enabled and a parameter that requires grad, returns scores and descriptors
+with a grad_fn (_SuperPointTrain: csrc/superpoint_train.hip for the ten 3x3 layers and the descriptor sampling, the exact-fp32 GEMM of
+train.py for the two 1x1 heads, tensor algebra for the softmax / L2-norm derivatives at coarse resolution).  Same values as eval(), bit
+for bit; the selection stays the inference kernels and carries no gradient, as in the reference.
 """
 from __future__ import annotations
 
@@ -58,6 +63,10 @@ class SuperPointNet(nn.Module):
         self.convDb = nn.Conv2d(256, descriptor_dim, kernel_size=1, stride=1, padding=0)
         self._packed: Optional[torch.Tensor] = None
         self._packed_key = None
+        self._packed_grad: Optional[torch.Tensor] = None
+        self._packed_grad_key = None
+        self.keep_layer_grads = False                # debug: backward leaves the per-layer pre-activation gradients in self.layer_grads
+        self.layer_grads = {}
         self._load_weights(weights)
 
     def _load_weights(self, weights):
@@ -159,16 +168,189 @@ class SuperPointNet(nn.Module):
                   lafs.data_ptr(), scores.data_ptr(), descriptors.data_ptr(), _lib.STREAM)
         return lafs, scores, descriptors
 
-    @torch.no_grad()
+    def _differentiable(self) -> bool:
+        return self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+
+    def _pack_grad(self, device: torch.device) -> torch.Tensor:
+        """The data-gradient blob (weights transposed, taps flipped), repacked when a weight changes -- as _pack."""
+        ts = self._pack_tensors()
+        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
+        if self._packed_grad is not None and self._packed_grad_key == key:
+            return self._packed_grad
+        lib = _lib.load()
+        host = [t.detach().to("cpu", torch.float32).contiguous() for t in ts]
+        ptrs = (C.c_void_p * len(host))(*[h.data_ptr() for h in host])
+        blob = torch.empty(lib.og_superpoint_train_packed_bytes(self.descriptor_dim), dtype=torch.uint8)
+        _lib.check(lib.og_superpoint_train_pack(self.descriptor_dim, ptrs, blob.data_ptr()), "og_superpoint_train_pack")
+        self._packed_grad = blob.to(device)
+        self._packed_grad_key = key
+        return self._packed_grad
+
     def forward(self, image: torch.Tensor, mask=None):
-        """image [B, 1, H, W] -> lafs [B, N, 2, 3], scores [B, N], descriptors [B, N, 256] (mask is ignored, as in the reference)."""
+        """image [B, 1, H, W] -> lafs [B, N, 2, 3], scores [B, N], descriptors [B, N, 256] (mask is ignored, as in the reference).
+        In train() mode with grad enabled and a parameter that requires grad, scores and descriptors carry a grad_fn."""
         self._check(image)
+        if self._differentiable():
+            if self._batch_norm:
+                raise NotImplementedError(f"{type(self).__name__}: the backward is implemented for SuperPointNet only")
+            return _SuperPointTrain.apply(self, image, *self._pack_tensors())
+        with torch.no_grad():
+            B, _, H, W = image.shape
+            ws = self._workspace(B, H, W, image.device)
+            heat, desc = self.dense(image, ws)
+            counts, sidx, sscore, _ = self.detect(heat, ws)
+            n = int(counts[B].item())                   # the one synchronisation: every image keeps the same count (min_stack)
+            return self.describe(n, sidx, sscore, desc)
+
+
+# flat gradient buffer of og_superpoint_train_backward: (offset, shape) of weight and bias per entry of CONV_NAMES
+def _grad_slices():
+    chans = [(1, 64), (64, 64), (64, 64), (64, 64), (64, 128), (128, 128), (128, 128), (128, 128)]
+    out, o = {}, 0
+    for name, (ci, co) in zip(CONV_NAMES[:8], chans):
+        out[name] = ((o, (co, ci, 3, 3)), (o + co * ci * 9, (co,)))
+        o += co * ci * 9 + co
+    w = 256 * 128 * 9                                # heads: convPa rows 0..255, convDa rows 256..511 of one [512][128][9] block
+    out["convPa"] = ((o, (256, 128, 3, 3)), (o + 2 * w, (256,)))
+    out["convDa"] = ((o + w, (256, 128, 3, 3)), (o + 2 * w + 256, (256,)))
+    return out, o + 2 * w + 512
+
+
+_GRAD_SLICES, _GRAD_FLOATS = _grad_slices()
+_TRUNK = CONV_NAMES[:8]                              # first_layer of og_superpoint_train_backward: index into this list, 8 = heads only
+
+
+class _SuperPointTrain(torch.autograd.Function):
+    """SuperPointNet.forward with a backward.  Inputs: the module, the image, then weight and bias of CONV_NAMES in order."""
+
+    @staticmethod
+    def forward(ctx, net, image, *params):
         B, _, H, W = image.shape
-        ws = self._workspace(B, H, W, image.device)
-        heat, desc = self.dense(image, ws)
-        counts, sidx, sscore, _ = self.detect(heat, ws)
-        n = int(counts[B].item())                   # the one synchronisation: every image keeps the same count (min_stack)
-        return self.describe(n, sidx, sscore, desc)
+        dev = image.device
+        img = image.detach().to(torch.float32).contiguous()
+        packed = net._pack(dev)
+        lib = _lib.load()
+        nsaved = lib.og_superpoint_train_saved_bytes(B, H, W)
+        if nsaved == 0:
+            raise ValueError(f"SuperPoint: unsupported image batch [{B}, 1, {H}, {W}] (B * H * W <= 2^26)")
+        Hc, Wc = H // 8, W // 8
+        saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
+        heat = torch.empty(B, Hc * 8, Wc * 8, device=dev, dtype=torch.float32)
+        desc = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
+        _lib.call("og_superpoint_train_forward", dev, B, H, W, img.data_ptr(), packed.data_ptr(), saved.data_ptr(), heat.data_ptr(),
+                  desc.data_ptr(), _lib.STREAM)
+        counts, sidx, sscore, _ = net.detect(heat, net._workspace(B, H, W, dev))
+        n = int(counts[B].item())
+        lafs, scores, descriptors = net.describe(n, sidx, sscore, desc)
+        ctx.net, ctx.n, ctx.shape = net, n, (B, H, W)
+        ctx.save_for_backward(img, saved, desc, sidx, *params)
+        ctx.mark_non_differentiable(lafs)
+        return lafs, scores, descriptors
+
+    @staticmethod
+    def backward(ctx, _dlafs, dscores, ddesc):
+        from . import ops, train                     # train imports this package's modules; keep the import local
+        net, n, (B, H, W) = ctx.net, ctx.n, ctx.shape
+        img, saved, desc, sidx, *params = ctx.saved_tensors
+        need = {name: (ctx.needs_input_grad[2 + 2 * i], ctx.needs_input_grad[3 + 2 * i]) for i, name in enumerate(CONV_NAMES)}
+        P = {name: (params[2 * i], params[2 * i + 1]) for i, name in enumerate(CONV_NAMES)}
+        dev = img.device
+        grads = {name: [None, None] for name in CONV_NAMES}
+
+        def result():
+            out = []
+            for name in CONV_NAMES:
+                for k in (0, 1):
+                    g = grads[name][k]
+                    if need[name][k] and g is None:
+                        g = torch.zeros_like(P[name][k])
+                    out.append(g if need[name][k] else None)
+            return (None, None, *out)
+
+        if n == 0:                                   # no keypoint: every gradient is zero, nothing to launch
+            return result()
+        Hc, Wc = H // 8, W // 8
+        npix = B * Hc * Wc
+        hidden = saved[:npix * 512].view(npix, 512)
+        ws = torch.empty(_lib.load().og_superpoint_train_workspace_bytes(B, H, W, n), device=dev, dtype=torch.uint8)
+        trunk_first = next((i for i, name in enumerate(_TRUNK) if any(need[name])), 8)
+        need_hidden = trunk_first < 8 or any(need["convPa"]) or any(need["convDa"])
+        g_hidden = torch.zeros(npix, 512, device=dev, dtype=torch.float32)
+
+        # ---- detector head: scores are heatmap values at the kept pixels -> softmax over 65 -> convPb
+        if dscores is not None and (need_hidden or any(need["convPb"])):
+            dheat = torch.zeros(B, Hc * 8 * Wc * 8, device=dev, dtype=torch.float32)
+            dheat.scatter_(1, sidx[:, :n].long(), dscores.to(torch.float32))         # the kept pixels of an image are distinct
+            dp = dheat.view(B, Hc, 8, Wc, 8).permute(0, 1, 3, 2, 4).reshape(npix, 64)
+            Wp = torch.zeros(68, 256, device=dev, dtype=torch.float32)               # 65 rows padded to a multiple of 4 for the GEMMs
+            Wp[:65] = P["convPb"][0].detach().view(65, 256)
+            bp = torch.zeros(68, device=dev, dtype=torch.float32)
+            bp[:65] = P["convPb"][1].detach()
+            hP = hidden[:, :256].contiguous()
+            # softmax backward, dlogit_c = p_c (dp_c - s) with s = sum_k p_k dp_k, written so that a peaked cell does not cancel: a kept
+            # pixel is a local maximum, often with p_c close to 1, where dp_c - s = dp_c (1 - p_c) - (s - p_c dp_c) loses every digit in
+            # the textbook form.  1 - p_c = (the sum of the OTHER exponentials) / Z comes from an exclusive prefix and suffix sum (all
+            # terms positive); s - p_c dp_c is exactly 0 when the cell holds one keypoint.
+            # The logits span ~30 units where the heatmap is peaked, so one fp32 ulp of a logit is already 1e-6 of a probability: the
+            # 256-term products are recomputed as 16 exact-fp32 GEMMs over 16 channels each and summed, like everything that follows
+            # up to dlog, in float64 tensor algebra at coarse resolution.
+            part = ops.gemm_nt(hP.view(npix, 16, 16).permute(1, 0, 2).contiguous(), Wp.view(68, 16, 16).permute(1, 0, 2).contiguous())
+            logit = part.double().sum(0)[:, :65] + bp[:65].double()
+            dp = dp.double()
+            e = torch.exp(logit - logit.max(dim=1, keepdim=True).values)
+            zero = torch.zeros(npix, 1, device=dev, dtype=torch.float64)
+            before = torch.cat([zero, torch.cumsum(e, 1)[:, :-1]], 1)
+            after = torch.cat([torch.cumsum(e.flip(1), 1)[:, :-1].flip(1), zero], 1)
+            Z = before[:, -1:] + e[:, -1:]
+            prob, rest = e / Z, (before + after) / Z
+            dp65 = torch.cat([dp, zero], 1)                                         # the dustbin channel receives no gradient
+            pd = prob * dp65
+            dlog = torch.zeros(npix, 68, device=dev, dtype=torch.float32)
+            dlog[:, :65] = prob * (dp65 * rest - (pd.sum(1, keepdim=True) - pd))
+            dh, dW, db = train._conv_backward(hP, Wp, dlog, need_hidden, any(need["convPb"]))
+            if any(need["convPb"]):
+                grads["convPb"] = [dW[:65].reshape(65, 256, 1, 1).contiguous(), db[:65].contiguous()]
+            if need_hidden:
+                g_hidden[:, :256] = dh
+
+        # ---- descriptor head: F.normalize + bilinear sampling (kernels) -> per-cell L2 norm -> convDb
+        if ddesc is not None and (need_hidden or any(need["convDb"])):
+            dd = ddesc.to(torch.float32).contiguous()
+            dcoarse = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
+            _lib.call("og_superpoint_describe_backward", dev, B, Hc, Wc, n, sidx.data_ptr(), sidx.shape[1], desc.data_ptr(), dd.data_ptr(),
+                      dcoarse.data_ptr(), ws.data_ptr() + (-ws.data_ptr()) % 256, _lib.STREAM)
+            Wd, bd = P["convDb"][0].detach().view(256, 256).contiguous(), P["convDb"][1].detach()
+            hD = hidden[:, 256:].contiguous()
+            nrm = torch.linalg.vector_norm(ops.gemm_nt(hD, Wd, bd), dim=1, keepdim=True)
+            dn, dc = desc.view(npix, 256), dcoarse.view(npix, 256)
+            draw = (dc - dn * (dn * dc).sum(1, keepdim=True)) / nrm
+            dh, dW, db = train._conv_backward(hD, Wd, draw, need_hidden, any(need["convDb"]))
+            if any(need["convDb"]):
+                grads["convDb"] = [dW.reshape(256, 256, 1, 1), db]
+            if need_hidden:
+                g_hidden[:, 256:] = dh
+
+        # ---- the ten 3x3 layers
+        if need_hidden:
+            g_hidden = g_hidden * (hidden > 0)       # ReLU of convPa | convDa
+            flat = torch.empty(_GRAD_FLOATS, device=dev, dtype=torch.float32)
+            dbg = None
+            if net.keep_layer_grads:
+                lv = [(H, W, 64), (H // 2, W // 2, 64), (H // 2, W // 2, 64), (H // 4, W // 4, 128), (H // 4, W // 4, 128),
+                      (Hc, Wc, 128), (Hc, Wc, 128), (Hc, Wc, 512)]
+                dbg = torch.zeros(sum(B * h * w * c for h, w, c in lv), device=dev, dtype=torch.float32)
+            _lib.call("og_superpoint_train_backward", dev, B, H, W, img.data_ptr(), net._pack_grad(dev).data_ptr(), saved.data_ptr(),
+                      g_hidden.data_ptr(), trunk_first, flat.data_ptr(), _lib.ptr(dbg), ws.data_ptr() + (-ws.data_ptr()) % 256, _lib.STREAM)
+            for name in _TRUNK[trunk_first:] + ["convPa", "convDa"]:
+                (ow, sw), (ob, sb) = _GRAD_SLICES[name]
+                nw = sw[0] * sw[1] * 9
+                grads[name] = [flat[ow:ow + nw].view(sw), flat[ob:ob + sb[0]]]
+            if dbg is not None:
+                net.layer_grads, o = {}, 0
+                for name, (h, w, c) in zip(_TRUNK[1:] + ["heads"], lv):
+                    net.layer_grads[name] = dbg[o:o + B * h * w * c].view(B, h, w, c)
+                    o += B * h * w * c
+        return result()
 
 
 class SuperPointNetBn(SuperPointNet):
