@@ -11,7 +11,7 @@
 //                (sp_conv3x3_save_kernel).  Saved: the post-ReLU output of every 3x3 layer, pooled and unpooled.
 //   dgrad        G_{j-1} = (3x3 convolution of G_j with the weights transposed and the taps flipped) masked by x_j > 0: the K loop of
 //                the forward kernel with a second packed blob, G_j read through sp_grad_at, the ReLU mask of the layer below in the
-//                store.
+//                store; every pass of 32 channels x 9 taps is summed on its own and then added to the total (K is up to 9 x 512).
 //   wgrad        dW[co][ci][tap] = sum over pixels of G[p][co] x[p + tap][ci]: a workgroup owns a 32 x 32 (co, ci) block and all nine
 //                taps over a contiguous range of 8 x 16 pixel tiles (split-K over pixels); per tile dy [128][32] and the x halo
 //                [180][32] are staged in LDS, each wave takes two tile rows as 16 k-steps x 9 taps of MFMA.  The waves are summed in
@@ -31,7 +31,7 @@ constexpr bool kPooled[SP_LAYERS] = {true, false, true, false, true, false, fals
 
 // ---------------------------------------------------------------- the K loop of the 3x3 convolution for any source of input pixels
 // load(gy, gx, c) returns channels c .. c + 3 of pixel (gy, gx) of the workgroup's image (called for pixels inside the image only; the
-// halo outside is zero).  Same tiling, packed-weight order and MFMA sequence as sp_conv3x3_kernel, hence the same bits.  (Routing the
+// halo outside is zero).  Same tiling, packed-weight order and, unless CHUNKED, MFMA sequence as sp_conv3x3_kernel, hence the same bits.  (Routing the
 // inference kernel itself through this function costs it an occupancy step -- 116 -> 162 VGPRs at BN = 128 -- so it keeps its body.)
 struct SpTile {
     int b, ty0, tx0, n0;         // image, first row / column of the 8 x 16 tile, first output channel
@@ -53,7 +53,10 @@ __device__ __forceinline__ SpTile sp_tile(int H, int W, int BN) {
     return t;
 }
 
-template <int BN, class Load>
+// CHUNKED (the data gradient): every pass of SP_KC input channels x 9 taps (288 products) is summed in an accumulator of its own and
+// then added to the total, instead of one chain over all 9 * Cin products.  With K = 9 x 512 at the heads a single fp32 chain is
+// 7 - 8x as far from float64 as ATen's blocked sums (tests/test_gpu_superpoint_train_forms.py); chunked it is a sum of 16 short chains.
+template <int BN, bool CHUNKED = false, class Load>
 __device__ __forceinline__ void sp_conv3x3_accumulate(Load load, const float* __restrict__ wp, int H, int W, int Cin, const SpTile& t,
                                                       float* tile, f32x16 (&acc)[2][BN / 64]) {
     constexpr int TM = 2, TN = BN / 64;
@@ -95,6 +98,15 @@ __device__ __forceinline__ void sp_conv3x3_accumulate(Load load, const float* __
             *reinterpret_cast<f32x4*>(&tile[p * SP_LDSC + q * 4]) = v;
         }
         __syncthreads();
+        f32x16 part[TM][TN];                         // CHUNKED: this pass alone
+        if constexpr (CHUNKED) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) part[i][j][r] = 0.f;
+        }
         for (int tap = 0; tap < 9; ++tap) {
             const int toff = ((tap / 3) * SP_HALO_W + (tap % 3)) * SP_LDSC;
 #pragma unroll
@@ -111,11 +123,21 @@ __device__ __forceinline__ void sp_conv3x3_accumulate(Load load, const float* __
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int j = 0; j < TN; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], bcur[j][e], acc[i][j], 0, 0, 0);
+                        for (int j = 0; j < TN; ++j) {
+                            if constexpr (CHUNKED) part[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], bcur[j][e], part[i][j], 0, 0, 0);
+                            else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], bcur[j][e], acc[i][j], 0, 0, 0);
+                        }
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bcur[j] = bnext[j];
             }
+        }
+        if constexpr (CHUNKED) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[i][j][r] += part[i][j][r];
         }
     }
 }
@@ -219,7 +241,7 @@ __global__ __launch_bounds__(256, 2) void sp_dgrad_kernel(const float* __restric
     const SpTile t = sp_tile(H, W, BN);
     const int b = t.b, lane = t.lane;
     f32x16 acc[TM][TN];
-    sp_conv3x3_accumulate<BN>([=](int gy, int gx, int c) { return sp_grad_at<POOLED>(g, a, b, H, W, Cg, gy, gx, c); }, wp, H, W, Cg, t, tile, acc);
+    sp_conv3x3_accumulate<BN, true>([=](int gy, int gx, int c) { return sp_grad_at<POOLED>(g, a, b, H, W, Cg, gy, gx, c); }, wp, H, W, Cg, t, tile, acc);
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int co = t.n0 + t.wn * (BN / 2) + j * 32 + (lane & 31);

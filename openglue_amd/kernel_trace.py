@@ -1,5 +1,5 @@
 """Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py, tests/test_gpu_gemm_forms.py, tests/test_gpu_proj_mlp_forms.py,
-tests/test_gpu_attention_backward.py, tests/test_gpu_sinkhorn_forms.py) and the form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
+tests/test_gpu_attention_backward.py, tests/test_gpu_sinkhorn_forms.py, tests/test_gpu_superpoint_train_forms.py) and the form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
 their own.
 
 launched_kernels(fn) runs fn() under torch.profiler (ProfilerActivity.CUDA: on ROCm, kineto's roctracer records every dispatched kernel
@@ -18,6 +18,8 @@ PROJ_MLP = ("mlp_small_kernel<", "mlp_fused_kernel<", "proj_small_kernel<", "pro
 ATTENTION_TRAIN = ("attention_bwd_kernel<", "attention_lse_kernel<", "attention_delta_kernel")     # csrc/attention_train.hip
 SINKHORN = ("sinkhorn_sweep_kernel<", "sinkhorn_sweep_fast_kernel<", "sinkhorn_combine_kernel<", "sinkhorn_combine_fast_kernel<", "sinkhorn_scores_kernel<",
             "sinkhorn_resident_kernel<", "sinkhorn_fallback_kernel<")     # csrc/sinkhorn.hip, csrc/sinkhorn_resident.hip: the inference Sinkhorn
+SUPERPOINT_TRAIN = ("sp_conv3x3_save_kernel<", "sp_dgrad_kernel<", "sp_wgrad_kernel<", "sp_wgrad1a_kernel", "sp_reduce_parts_kernel", "sp_describe_bwd_point_kernel",
+                    "sp_describe_bwd_cell_kernel", "sp_grad_dump_kernel<")     # csrc/superpoint_train.hip: the SuperPoint fine-tuning kernels
 PROJ_WSTAT = "proj_wstat_kernel"       # csrc/proj_wstat.hip: the weight-stationary q | k | v projection of 256-d batches (no template arguments)
 
 
@@ -84,3 +86,8 @@ def attention_train_instances(names) -> list:
 def sinkhorn_instances(names) -> list:
     """The inference-Sinkhorn launches (csrc/sinkhorn.hip, csrc/sinkhorn_resident.hip) among `names`, in launch order, one entry per launch."""
     return [n for n in names if n.startswith(SINKHORN)]
+
+
+def superpoint_train_instances(names) -> list:
+    """The SuperPoint fine-tuning launches (csrc/superpoint_train.hip) among `names`, in launch order, one entry per launch."""
+    return [n for n in names if n.startswith(SUPERPOINT_TRAIN)]
