@@ -416,8 +416,7 @@ struct Roctx {
     int (*push)(const char*) = nullptr;
     int (*pop)() = nullptr;
     Roctx() {
-        const char* e = getenv("OG_ROCTX");
-        if (!e || e[0] != '1') return;
+        if (!og_knob_roctx()) return;
         for (const char* name : {"librocprofiler-sdk-roctx.so", "librocprofiler-sdk-roctx.so.1", "libroctx64.so", "libroctx64.so.4"}) {
             void* h = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
             if (!h) continue;
@@ -444,10 +443,19 @@ struct Scope {
     ~Scope() { if (p) p->end(i); }
 };
 
+// what a forward pass does besides og_forward's own: every entry point names what it sets
+struct ForwardOpts {
+    Profiler* prof = nullptr;                   // og_forward*_profiled: per-stage events
+    const RaggedDesc* rag = nullptr;            // ragged batch: the per-pair descriptor ...
+    const EncoderRagged *er0 = nullptr, *er1 = nullptr;      // ... and each side's keypoint-encoder descriptor
+    int tap = -1; float* tap_x = nullptr;       // og_forward_tap: copy the residual stream at this stage boundary to tap_x
+    bool encoder_only = false;                  // og_keypoint_encoder: stop after tap 0
+};
+
 int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev,
-                 const og_outputs* outp, void* stream, Profiler* prof, const RaggedDesc* rag = nullptr,
-                 const EncoderRagged* er0 = nullptr, const EncoderRagged* er1 = nullptr, int tap = -1, float* tap_x = nullptr,
-                 bool encoder_only = false) {
+                 const og_outputs* outp, void* stream, const ForwardOpts& opts) {
+    Profiler* const prof = opts.prof; const RaggedDesc* const rag = opts.rag; const EncoderRagged* const er0 = opts.er0; const EncoderRagged* const er1 = opts.er1;
+    const int tap = opts.tap; float* const tap_x = opts.tap_x; const bool encoder_only = opts.encoder_only;
     static const og_outputs no_outputs{};
     if (encoder_only && !outp) outp = &no_outputs;          // og_keypoint_encoder: stops after tap 0, writes nothing but tap_x
     if (!shape || !in || !packed_dev || !workspace_dev || !outp) return OG_E_INVALID;
@@ -587,12 +595,8 @@ int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_
     // q / k / v projections of token rows [r0, r0 + R): columns [c0, c1) of the q | k | v planes = rows [c0, c1) of the packed
     // projection matrix.  One launch; with favor_relu the feature blocks (columns < 2 WQ) carry the ReLU of the feature map and the
     // value block does not, so a range that spans both is two launches.
-    // Few rows (<= 8192 per launch, the single-pair regime): proj_small_kernel, 32-token workgroups over a fragment-major copy of the
-    // matrix -- 17.5 us per launch of the 128-token tile GEMM otherwise, 36 launches per step.  OG_PROJ_SMALL=0 / 1 forces.
-    auto proj_small_ok = [&](int64_t R) {
-        static const int mode = [] { const char* e = getenv("OG_PROJ_SMALL"); return e ? atoi(e) : -1; }();
-        return L.o_wqkvs >= 0 && !favor && (mode >= 0 ? mode != 0 : R <= 8192) && R < ((int64_t)1 << 30);
-    };
+    // Few rows: proj_small_kernel (og_proj_small_wanted).
+    auto proj_small_ok = [&](int64_t R) { return L.o_wqkvs >= 0 && !favor && og_proj_small_wanted(R) && R < ((int64_t)1 << 30); };
     auto proj_small = [&](const float* lw, int64_t r0, int64_t R, int split_row, int a0, int a1, int b0, int b1) -> int {
         Scope sc(prof, OG_STAGE_GEMM_F16X3);
         return og_launch_proj_small(XO + r0 * D4, D4, (int)R, D, (const char*)(lw + L.o_wqkvs), lw + L.o_bqkv, lw + L.o_scale,
@@ -762,40 +766,6 @@ int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_
     return 0;
 }
 
-}  // namespace
-
-extern "C" int og_forward(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev,
-                          const og_outputs* outp, void* stream) {
-    return forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, nullptr);
-}
-
-extern "C" int og_forward_ragged(const og_shape* shape, const int32_t* lens0, const int32_t* lens1, const float* image0_wh,
-                                 const float* image1_wh, const og_inputs* in, const void* packed_dev, void* workspace_dev,
-                                 const og_outputs* outp, void* stream);
-
-// include/openglue_amd.h: og_forward plus a copy of the residual stream at one stage boundary (per-stage parity tests)
-extern "C" int og_forward_tap(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev,
-                              const og_outputs* outp, void* stream, int32_t tap, float* tap_x) {
-    if (!shape || tap < 0 || tap > 2 * shape->num_stages || !tap_x || ((uintptr_t)tap_x & 15)) return OG_E_INVALID;
-    return forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, nullptr, nullptr, nullptr, nullptr, tap, tap_x);
-}
-
-// include/openglue_amd.h: the keypoint-encoder stage on its own (SURVEY.md 8b names it among the per-stage entries)
-extern "C" int og_keypoint_encoder(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev, float* x_out,
-                                   void* stream) {
-    if (!shape || !x_out || ((uintptr_t)x_out & 15)) return OG_E_INVALID;
-    return forward_impl(shape, in, packed_dev, workspace_dev, nullptr, stream, nullptr, nullptr, nullptr, nullptr, 0, x_out, true);
-}
-
-// include/openglue_amd.h: the raw score matrices of a batch of pairs, exact fp32 (the whole path forms them from (hi, lo) rows it already holds)
-extern "C" int og_scores(const float* g0, const float* g1, int32_t batch, int32_t m, int32_t n, int32_t D, float* S, int64_t lds, void* stream) {
-    if (!g0 || !g1 || !S || batch <= 0 || m <= 0 || n <= 0 || D <= 0) return OG_E_INVALID;
-    if ((D & 3) || lds < n || (lds & 3)) return OG_E_SHAPE;
-    return og_gemm_nt(g0, D, (int64_t)m * D, g1, D, (int64_t)n * D, S, lds, (int64_t)m * lds, m, n, D, batch, nullptr, 0, nullptr, 0, nullptr,
-                      (float)pow((double)D, -0.5), stream);
-}
-
-namespace {
 int build_ragged(const og_shape* shape, const int32_t* lens0, const int32_t* lens1, const float* image0_wh, const float* image1_wh,
                  const og_inputs* in, RaggedDesc& rd, EncoderRagged& er0, EncoderRagged& er1) {
     if (!shape || !lens0 || !lens1 || !in) return OG_E_INVALID;
@@ -818,32 +788,13 @@ int build_ragged(const og_shape* shape, const int32_t* lens0, const int32_t* len
     return 0;
 }
 
+// forward_impl under a Profiler: the per-stage times and launch counts of og_forward_profiled / og_forward_ragged_profiled
 int profiled(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev, const og_outputs* outp,
-             void* stream, float* stage_ms, int32_t* stage_launches, const RaggedDesc* rd, const EncoderRagged* er0,
-             const EncoderRagged* er1);
-}  // namespace
-
-extern "C" int og_forward_profiled(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev,
-                                   const og_outputs* outp, void* stream, float* stage_ms, int32_t* stage_launches) {
-    return profiled(shape, in, packed_dev, workspace_dev, outp, stream, stage_ms, stage_launches, nullptr, nullptr, nullptr);
-}
-
-extern "C" int og_forward_ragged_profiled(const og_shape* shape, const int32_t* lens0, const int32_t* lens1, const float* image0_wh,
-                                          const float* image1_wh, const og_inputs* in, const void* packed_dev, void* workspace_dev,
-                                          const og_outputs* outp, void* stream, float* stage_ms, int32_t* stage_launches) {
-    RaggedDesc rd;
-    EncoderRagged er0, er1;
-    if (int e = build_ragged(shape, lens0, lens1, image0_wh, image1_wh, in, rd, er0, er1)) return e;
-    return profiled(shape, in, packed_dev, workspace_dev, outp, stream, stage_ms, stage_launches, &rd, &er0, &er1);
-}
-
-namespace {
-int profiled(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev, const og_outputs* outp,
-             void* stream, float* stage_ms, int32_t* stage_launches, const RaggedDesc* rd, const EncoderRagged* er0,
-             const EncoderRagged* er1) {
+             void* stream, float* stage_ms, int32_t* stage_launches, ForwardOpts opts) {
     if (!stage_ms || !stage_launches) return OG_E_INVALID;
     Profiler prof{(hipStream_t)stream, {}, {}};
-    int rc = forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, &prof, rd, er0, er1);
+    opts.prof = &prof;
+    int rc = forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, opts);
     hipError_t e = hipStreamSynchronize((hipStream_t)stream);
     for (int c = 0; c < OG_NUM_STAGES; ++c) { stage_ms[c] = 0.f; stage_launches[c] = 0; }
     for (size_t i = 0; i < prof.cls.size(); ++i) {
@@ -858,13 +809,57 @@ int profiled(const og_shape* shape, const og_inputs* in, const void* packed_dev,
     if (rc) return rc;
     return e == hipSuccess ? 0 : (int)e;
 }
+
 }  // namespace
+
+extern "C" int og_forward(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev,
+                          const og_outputs* outp, void* stream) {
+    return forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, ForwardOpts{});
+}
 
 extern "C" int og_forward_ragged(const og_shape* shape, const int32_t* lens0, const int32_t* lens1, const float* image0_wh,
                                  const float* image1_wh, const og_inputs* in, const void* packed_dev, void* workspace_dev,
                                  const og_outputs* outp, void* stream) {
-    RaggedDesc rd;
-    EncoderRagged er0, er1;
+    RaggedDesc rd; EncoderRagged er0, er1;
     if (int e = build_ragged(shape, lens0, lens1, image0_wh, image1_wh, in, rd, er0, er1)) return e;
-    return forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, nullptr, &rd, &er0, &er1);
+    ForwardOpts opts; opts.rag = &rd; opts.er0 = &er0; opts.er1 = &er1;
+    return forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, opts);
+}
+
+// include/openglue_amd.h: og_forward plus a copy of the residual stream at one stage boundary (per-stage parity tests)
+extern "C" int og_forward_tap(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev,
+                              const og_outputs* outp, void* stream, int32_t tap, float* tap_x) {
+    if (!shape || tap < 0 || tap > 2 * shape->num_stages || !tap_x || ((uintptr_t)tap_x & 15)) return OG_E_INVALID;
+    ForwardOpts opts; opts.tap = tap; opts.tap_x = tap_x;
+    return forward_impl(shape, in, packed_dev, workspace_dev, outp, stream, opts);
+}
+
+// include/openglue_amd.h: the keypoint-encoder stage on its own (SURVEY.md 8b names it among the per-stage entries)
+extern "C" int og_keypoint_encoder(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev, float* x_out,
+                                   void* stream) {
+    if (!shape || !x_out || ((uintptr_t)x_out & 15)) return OG_E_INVALID;
+    ForwardOpts opts; opts.tap = 0; opts.tap_x = x_out; opts.encoder_only = true;
+    return forward_impl(shape, in, packed_dev, workspace_dev, nullptr, stream, opts);
+}
+
+// include/openglue_amd.h: the raw score matrices of a batch of pairs, exact fp32 (the whole path forms them from (hi, lo) rows it already holds)
+extern "C" int og_scores(const float* g0, const float* g1, int32_t batch, int32_t m, int32_t n, int32_t D, float* S, int64_t lds, void* stream) {
+    if (!g0 || !g1 || !S || batch <= 0 || m <= 0 || n <= 0 || D <= 0) return OG_E_INVALID;
+    if ((D & 3) || lds < n || (lds & 3)) return OG_E_SHAPE;
+    return og_gemm_nt(g0, D, (int64_t)m * D, g1, D, (int64_t)n * D, S, lds, (int64_t)m * lds, m, n, D, batch, nullptr, 0, nullptr, 0, nullptr,
+                      (float)pow((double)D, -0.5), stream);
+}
+
+extern "C" int og_forward_profiled(const og_shape* shape, const og_inputs* in, const void* packed_dev, void* workspace_dev,
+                                   const og_outputs* outp, void* stream, float* stage_ms, int32_t* stage_launches) {
+    return profiled(shape, in, packed_dev, workspace_dev, outp, stream, stage_ms, stage_launches, ForwardOpts{});
+}
+
+extern "C" int og_forward_ragged_profiled(const og_shape* shape, const int32_t* lens0, const int32_t* lens1, const float* image0_wh,
+                                          const float* image1_wh, const og_inputs* in, const void* packed_dev, void* workspace_dev,
+                                          const og_outputs* outp, void* stream, float* stage_ms, int32_t* stage_launches) {
+    RaggedDesc rd; EncoderRagged er0, er1;
+    if (int e = build_ragged(shape, lens0, lens1, image0_wh, image1_wh, in, rd, er0, er1)) return e;
+    ForwardOpts opts; opts.rag = &rd; opts.er0 = &er0; opts.er1 = &er1;
+    return profiled(shape, in, packed_dev, workspace_dev, outp, stream, stage_ms, stage_launches, opts);
 }

@@ -2044,159 +2044,117 @@ __global__ __launch_bounds__(256, 2) void attention_p16_kernel(AttnArgs a, RD rd
 
 }  // namespace
 
+#ifndef OG_ATTN_PIPE8
+#define OG_ATTN_PIPE8 0      // experiment build (scripts/build_attn_ablation.sh pipe8 -DOG_ATTN_PIPE8=1): instantiates the eight-wave form, OG_ATTN_PIPE=2 selects it.
+#endif                       // Measured (profiles/r06_j_attention_pipe8_ab.log): parity as the other forms, 230 vs 221 us at the C2 shape, 840 vs 773 us at 2048 keys.
+
+namespace {          // host side: og_launch_attention validates, selects (attn_plan) and launches
+// REG: attention_kernel (register-staged, any head size); P16: attention_p16_kernel; the others are forms of attention_dma_kernel (dh = 64 / 32)
+enum class AttnFamily { REG, DMA, KSPLIT, GSPLIT2, GSPLIT4, MX, P16, PIPE, PIPE8 };
+struct AttnPlan {
+    int status = 0;          // OG_E_INVALID: a group in use is empty; OG_E_SHAPE: no kernel takes this head size / form
+    AttnFamily family = AttnFamily::REG;
+    dim3 grid, block = dim3(256);
+    int qtiles = 0, gs_scatter = 0;      // AttnArgs::qtiles and (grid-split launches) AttnArgs::gs_scatter of the launch
+};
+
+// Which kernel family takes the launch, with what grid.  In order of precedence: grid split, key split, MX, P16, PIPE8, PIPE, then the
+// plain LDS-DMA kernel at dh = 64 / 32 and the register-staged one elsewhere.
+AttnPlan attn_plan(const AttnArgs& a) {
+    AttnPlan p;
+    int nqmax = 0, nkmin = 1 << 30;          // over the groups in use
+    for (int g = 0; g < 2; ++g) {
+        if (!(g == 0 ? a.split > 0 : a.split < a.nz)) continue;
+        if (a.nq[g] <= 0 || a.nk[g] <= 0) { p.status = OG_E_INVALID; return p; }
+        if (a.nq[g] > nqmax) nqmax = a.nq[g];
+        if (a.nk[g] < nkmin) nkmin = a.nk[g];
+    }
+    p.qtiles = (nqmax + Q_TILE - 1) / Q_TILE;
+    const int groups8 = (a.nz * a.num_heads + 7) / 8 * 8;
+    const int wgs = groups8 * p.qtiles;
+    p.grid = dim3(wgs);
+    // dh = 64 / 32 -- head rows of one or half a 128-byte line: the LDS-DMA kernel (OG_ATTN_DMA=0 keeps the register-staged one, for A/B runs)
+    const bool dma = og_knob_attn_dma() && (a.dh == 64 || a.dh == 32);
+    // One or two pairs (the grid covers at most half of the CUs) and scratch at hand: the key tiles of a query tile go to 2 or 4 workgroups
+    // (attention_dma_kernel<., ., 1, GS>).  OG_ATTN_GSPLIT=0 / 2 / 4 forces.
+    const int gs_mode = og_knob_attn_gsplit();
+    int gs = 1;
+    if (!a.mx && dma && a.partial && a.counters && wgs <= OG_ATTN_COUNTERS) {
+        // The split launch may hold up to two workgroups per CU at dh = 32 (they do not wait for each other: the last arriver of a query tile merges),
+        // one at dh = 64 -- measured in one call (profiles/r05_j_bench_attn_gsplit_maxwg_ab.jsonl): dh = 32, 512 against 256 workgroups: a single
+        // 2048-keypoint pair 1.428 -> 1.394 ms per step, two pairs 1.703 -> 1.640, one 4096-keypoint pair 3.47 -> 3.24; dh = 64: one pair +-0, two pairs
+        // 1.962 -> 1.997, four 2.385 -> 2.427 (slower).  OG_ATTN_GS_MAXWG overrides (experiments).
+        const int maxwg = og_knob_attn_gs_maxwg() > 0 ? og_knob_attn_gs_maxwg() : (a.dh == 32 ? 512 : 256);
+        if (gs_mode >= 0) gs = gs_mode == 2 || gs_mode == 4 ? gs_mode : 1;
+        else if (wgs * 4 <= maxwg && (a.rag || nkmin >= 16 * KV_TILE)) gs = 4;
+        else if (wgs * 2 <= maxwg && (a.rag || nkmin >= 8 * KV_TILE)) gs = 2;
+        if (wgs * gs > maxwg && gs_mode < 0) gs = 1;
+        if ((int64_t)wgs * gs * 4 * 34 * 64 > OG_ATTN_PARTIAL_FLOATS) gs = 1;
+    }
+    const int ks_mode = og_knob_attn_ksplit(), pipe_mode = og_knob_attn_pipe();
+    if (gs > 1) {          // (dh = 32, round 5: a single 2048-keypoint pair of the 128-d family = 128 workgroups of 32 key tiles each without the split)
+        p.family = gs == 4 ? AttnFamily::GSPLIT4 : AttnFamily::GSPLIT2;
+        p.grid = dim3(wgs * gs);
+        p.gs_scatter = og_knob_attn_gs_scatter();      // read per launch, so that one process can compare both placements
+    // Few workgroups (at most one per CU) and enough keys: the key range of a query tile is split over the two halves of an 8-wave
+    // workgroup (attention_dma_kernel<64, ., 2>).  OG_ATTN_KSPLIT=0 / 1 forces.
+    } else if (!a.mx && dma && a.dh == 64 && (ks_mode >= 0 ? ks_mode != 0 : (wgs <= 256 && (a.rag || nkmin >= 4 * KV_TILE)))) {
+        p.family = AttnFamily::KSPLIT; p.block = dim3(512);
+    } else if (a.mx) {          // 8-bit P V cross products: batch form of the LDS-DMA kernel only (the callers set mx only where the producers wrote the 8-bit rows)
+        p.family = AttnFamily::MX; p.status = dma ? 0 : OG_E_SHAPE;
+    } else if (dma && a.dh == 64 && og_knob_attn_p16() > 0) {          // the 16x16x32 pipelined kernel (dh = 64, batch form): OG_ATTN_P16=0 / 1
+        p.family = AttnFamily::P16;
+    } else if (OG_ATTN_PIPE8 && dma && pipe_mode == 2 && a.dh == 64) {          // eight waves, 256 queries per workgroup
+        p.family = AttnFamily::PIPE8;
+        p.qtiles = (nqmax + 2 * Q_TILE - 1) / (2 * Q_TILE);
+        p.grid = dim3(groups8 * p.qtiles); p.block = dim3(512);
+    } else if (dma) {          // the software-pipelined tile loop (PIPE) for the batch form: OG_ATTN_PIPE=0 / 1
+        p.family = pipe_mode > 0 ? AttnFamily::PIPE : AttnFamily::DMA;
+    } else if (a.dh != 16 && a.dh != 32 && a.dh != 64 && a.dh != 128) {
+        p.status = OG_E_SHAPE;
+    }
+    return p;
+}
+
+}  // namespace
+
 int og_launch_attention(const AttnArgs& a, hipStream_t stream) {
     if (!a.qh || !a.ql || !a.kh || !a.kl || !a.vh || !a.vl || !a.oh || !a.ol || a.nz <= 0 || a.num_heads <= 0) return OG_E_INVALID;
     if ((a.ldq & 7) || (a.ldk & 7) || (a.ldv & 7) || (a.ldo & 3)) return OG_E_ALIGN;
     const void* ps[8] = {a.qh, a.ql, a.kh, a.kl, a.vh, a.vl, a.oh, a.ol};
     for (int i = 0; i < 8; ++i)
         if ((uintptr_t)ps[i] & 15) return OG_E_ALIGN;
-    int nqmax = 0;
-    for (int g = 0; g < 2; ++g) {
-        const bool used = g == 0 ? a.split > 0 : a.split < a.nz;
-        if (!used) continue;
-        if (a.nq[g] <= 0 || a.nk[g] <= 0) return OG_E_INVALID;
-        if (a.nq[g] > nqmax) nqmax = a.nq[g];
-    }
+    const AttnPlan p = attn_plan(a);
+    if (p.status) return p.status;
     AttnArgs a2 = a;
-    a2.qtiles = (nqmax + Q_TILE - 1) / Q_TILE;
-    RaggedDesc rd;
-    rd.B = 0;
-    if (a.rag) rd = *a.rag;
-    a2.rag = nullptr;
-    // dh = 64 with full-line head rows: the LDS-DMA kernel (OG_ATTN_DMA=0 keeps the register-staged one, for A/B runs)
-    static const bool dma_on = [] { const char* e = getenv("OG_ATTN_DMA"); return !(e && e[0] == '0'); }();
-    const bool dma = dma_on && (a.dh == 64 || a.dh == 32);       // head rows of one or half a 128-byte line: the LDS-DMA kernel
-    const int groups8 = (a.nz * a.num_heads + 7) / 8 * 8;
-    dim3 grid(groups8 * a2.qtiles), block(256);
-    // Few workgroups (at most one per CU) and enough keys: the key range of a query tile is split over the two halves of an 8-wave
-    // workgroup (attention_dma_kernel<64, ., 2>).  OG_ATTN_KSPLIT=0 / 1 forces.
-    static const int ks_mode = [] { const char* e = getenv("OG_ATTN_KSPLIT"); return e ? atoi(e) : -1; }();
-    int nkmin = 1 << 30;
-    for (int g = 0; g < 2; ++g) {
-        const bool used = g == 0 ? a.split > 0 : a.split < a.nz;
-        if (used && a.nk[g] < nkmin) nkmin = a.nk[g];
-    }
-    // One or two pairs (the grid covers at most half of the CUs) and scratch at hand: the key tiles of a query tile go to 2 or 4 workgroups
-    // (attention_dma_kernel<64, ., 1, GS>).  OG_ATTN_GSPLIT=0 / 2 / 4 forces.
-    static const int gs_mode = [] { const char* e = getenv("OG_ATTN_GSPLIT"); return e ? atoi(e) : -1; }();
-    int gs = 1;
-    if (!a.mx && dma && (a.dh == 64 || a.dh == 32) && a.partial && a.counters && (int)grid.x <= OG_ATTN_COUNTERS) {
-        // The split launch may hold up to two workgroups per CU at dh = 32 (they do not wait for each other: the last arriver of a query tile merges),
-        // one at dh = 64 -- measured in one call (profiles/r05_j_bench_attn_gsplit_maxwg_ab.jsonl): dh = 32, 512 against 256 workgroups: a single
-        // 2048-keypoint pair 1.428 -> 1.394 ms per step, two pairs 1.703 -> 1.640, one 4096-keypoint pair 3.47 -> 3.24; dh = 64: one pair +-0, two pairs
-        // 1.962 -> 1.997, four 2.385 -> 2.427 (slower).  OG_ATTN_GS_MAXWG overrides (experiments).
-        static const int maxwg_env = [] { const char* e = getenv("OG_ATTN_GS_MAXWG"); return e ? atoi(e) : 0; }();
-        const int maxwg = maxwg_env > 0 ? maxwg_env : (a.dh == 32 ? 512 : 256);
-        if (gs_mode >= 0) gs = gs_mode == 2 || gs_mode == 4 ? gs_mode : 1;
-        else if ((int)grid.x * 4 <= maxwg && (a.rag || nkmin >= 16 * KV_TILE)) gs = 4;
-        else if ((int)grid.x * 2 <= maxwg && (a.rag || nkmin >= 8 * KV_TILE)) gs = 2;
-        if ((int)grid.x * gs > maxwg && gs_mode < 0) gs = 1;
-        if ((int64_t)grid.x * gs * 4 * 34 * 64 > OG_ATTN_PARTIAL_FLOATS) gs = 1;
-    }
-    if (gs > 1) {
-        dim3 g2(grid.x * gs);
-        const char* const sc = getenv("OG_ATTN_GS_SCATTER");      // tests (read per launch, so that one process can compare both placements): deal the parts of a tile to different XCDs
-        a2.gs_scatter = sc && sc[0] == '1' ? 1 : 0;
-        if (a.dh == 64) {
-            if (a.rag) {
-                if (gs == 4) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedDesc, 1, 4>), g2, block, 0, stream, a2, rd);
-                else hipLaunchKernelGGL((attention_dma_kernel<64, RaggedDesc, 1, 2>), g2, block, 0, stream, a2, rd);
-            } else {
-                if (gs == 4) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedNone, 1, 4>), g2, block, 0, stream, a2, RaggedNone{});
-                else hipLaunchKernelGGL((attention_dma_kernel<64, RaggedNone, 1, 2>), g2, block, 0, stream, a2, RaggedNone{});
-            }
-        } else {          // dh = 32 (round 5): a single 2048-keypoint pair of the 128-d family = 128 workgroups of 32 key tiles each without the split
-            if (a.rag) {
-                if (gs == 4) hipLaunchKernelGGL((attention_dma_kernel<32, RaggedDesc, 1, 4>), g2, block, 0, stream, a2, rd);
-                else hipLaunchKernelGGL((attention_dma_kernel<32, RaggedDesc, 1, 2>), g2, block, 0, stream, a2, rd);
-            } else {
-                if (gs == 4) hipLaunchKernelGGL((attention_dma_kernel<32, RaggedNone, 1, 4>), g2, block, 0, stream, a2, RaggedNone{});
-                else hipLaunchKernelGGL((attention_dma_kernel<32, RaggedNone, 1, 2>), g2, block, 0, stream, a2, RaggedNone{});
-            }
-        }
-        return og_launch_status();
-    }
-    const bool ksplit = !a.mx && dma && a.dh == 64 && (ks_mode >= 0 ? ks_mode != 0 : ((int)grid.x <= 256 && (a.rag || nkmin >= 4 * KV_TILE)));
-    if (ksplit) {
-        if (a.rag) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedDesc, 2>), grid, dim3(512), 0, stream, a2, rd);
-        else hipLaunchKernelGGL((attention_dma_kernel<64, RaggedNone, 2>), grid, dim3(512), 0, stream, a2, RaggedNone{});
-        return og_launch_status();
-    }
-    if (a.mx) {          // 8-bit P V cross products: batch form of the LDS-DMA kernel only (the callers set mx only where the producers wrote the 8-bit rows)
-        if (!dma) return OG_E_SHAPE;
-        const int e = 127 + a.mx_sv - 11;
-        a2.mx_scale_a = e | (e << 8) | (e << 16) | (e << 24);
-        if (a.rag) {
-            if (a.dh == 64) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedDesc, 1, 1, 1>), grid, block, 0, stream, a2, rd);
-            else hipLaunchKernelGGL((attention_dma_kernel<32, RaggedDesc, 1, 1, 1>), grid, block, 0, stream, a2, rd);
-        } else {
-            if (a.dh == 64) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedNone, 1, 1, 1>), grid, block, 0, stream, a2, RaggedNone{});
-            else hipLaunchKernelGGL((attention_dma_kernel<32, RaggedNone, 1, 1, 1>), grid, block, 0, stream, a2, RaggedNone{});
-        }
-        return og_launch_status();
-    }
-    // the 16x16x32 pipelined kernel (dh = 64, batch form): OG_ATTN_P16=0 / 1
-    static const int p16_mode = [] { const char* e = getenv("OG_ATTN_P16"); return e ? atoi(e) : -1; }();
-    if (dma && a.dh == 64 && (p16_mode >= 0 ? p16_mode != 0 : false)) {
-        if (a.rag) hipLaunchKernelGGL((attention_p16_kernel<RaggedDesc>), grid, block, 0, stream, a2, rd);
-        else hipLaunchKernelGGL((attention_p16_kernel<RaggedNone>), grid, block, 0, stream, a2, RaggedNone{});
-        return og_launch_status();
-    }
-    // the software-pipelined tile loop (PIPE) for the batch form; OG_ATTN_PIPE=0 / 1 forces
-    static const int pipe_mode = [] { const char* e = getenv("OG_ATTN_PIPE"); return e ? atoi(e) : -1; }();
-    const bool pipe = dma && (pipe_mode >= 0 ? pipe_mode != 0 : false);
-#ifndef OG_ATTN_PIPE8
-#define OG_ATTN_PIPE8 0      // experiment build (scripts/build_attn_ablation.sh pipe8 -DOG_ATTN_PIPE8=1): instantiates the eight-wave form, OG_ATTN_PIPE=2 selects it.
-#endif                       // Measured (profiles/r06_j_attention_pipe8_ab.log): parity as the other forms, 230 vs 221 us at the C2 shape, 840 vs 773 us at 2048 keys.
+    a2.rag = nullptr; a2.qtiles = p.qtiles; a2.gs_scatter = p.gs_scatter;
+    if (const int e = 127 + a.mx_sv - 11; p.family == AttnFamily::MX) a2.mx_scale_a = e | (e << 8) | (e << 16) | (e << 24);
+    // The per-pair descriptor travels by value in the kernarg segment ONLY for ragged launches (og_common.h: RaggedNone).  Every kernel instance
+    // stands in exactly one statement.
+    auto launch = [&](auto rd) -> int {
+        using RD = decltype(rd);
+        auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, p.grid, p.block, 0, stream, a2, rd); };
+        const bool d64 = a.dh == 64;          // (the attention_dma_kernel families: dh = 64 or 32)
+        switch (p.family) {
+            case AttnFamily::GSPLIT4: d64 ? go(attention_dma_kernel<64, RD, 1, 4>) : go(attention_dma_kernel<32, RD, 1, 4>); break;
+            case AttnFamily::GSPLIT2: d64 ? go(attention_dma_kernel<64, RD, 1, 2>) : go(attention_dma_kernel<32, RD, 1, 2>); break;
+            case AttnFamily::KSPLIT: go(attention_dma_kernel<64, RD, 2>); break;
+            case AttnFamily::MX: d64 ? go(attention_dma_kernel<64, RD, 1, 1, 1>) : go(attention_dma_kernel<32, RD, 1, 1, 1>); break;
+            case AttnFamily::P16: go(attention_p16_kernel<RD>); break;
 #if OG_ATTN_PIPE8
-    if (pipe && pipe_mode == 2 && a.dh == 64) {          // eight waves, 256 queries per workgroup
-        a2.qtiles = (nqmax + 2 * Q_TILE - 1) / (2 * Q_TILE);
-        dim3 grid8(groups8 * a2.qtiles);
-        if (a.rag) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedDesc, 1, 1, 0, 2>), grid8, dim3(512), 0, stream, a2, rd);
-        else hipLaunchKernelGGL((attention_dma_kernel<64, RaggedNone, 1, 1, 0, 2>), grid8, dim3(512), 0, stream, a2, RaggedNone{});
-        return og_launch_status();
-    }
+            case AttnFamily::PIPE8: go(attention_dma_kernel<64, RD, 1, 1, 0, 2>); break;
 #endif
-    if (pipe) {
-        if (a.rag) {
-            if (a.dh == 64) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedDesc, 1, 1, 0, 1>), grid, block, 0, stream, a2, rd);
-            else hipLaunchKernelGGL((attention_dma_kernel<32, RaggedDesc, 1, 1, 0, 1>), grid, block, 0, stream, a2, rd);
-        } else {
-            if (a.dh == 64) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedNone, 1, 1, 0, 1>), grid, block, 0, stream, a2, RaggedNone{});
-            else hipLaunchKernelGGL((attention_dma_kernel<32, RaggedNone, 1, 1, 0, 1>), grid, block, 0, stream, a2, RaggedNone{});
+            case AttnFamily::PIPE: d64 ? go(attention_dma_kernel<64, RD, 1, 1, 0, 1>) : go(attention_dma_kernel<32, RD, 1, 1, 0, 1>); break;
+            case AttnFamily::DMA: d64 ? go(attention_dma_kernel<64, RD>) : go(attention_dma_kernel<32, RD>); break;
+            default:          // REG
+                if (a.dh == 16) go(attention_kernel<16, RD>);
+                else if (a.dh == 32) go(attention_kernel<32, RD>);
+                else if (a.dh == 64) go(attention_kernel<64, RD>);
+                else go(attention_kernel<128, RD>);
         }
         return og_launch_status();
-    }
-    if (a.rag) {
-        switch (a.dh) {
-            case 16: hipLaunchKernelGGL((attention_kernel<16, RaggedDesc>), grid, block, 0, stream, a2, rd); break;
-            case 128: hipLaunchKernelGGL((attention_kernel<128, RaggedDesc>), grid, block, 0, stream, a2, rd); break;      // register-staged kernel, generic in the head size
-            case 32:
-                if (dma) hipLaunchKernelGGL((attention_dma_kernel<32, RaggedDesc>), grid, block, 0, stream, a2, rd);
-                else hipLaunchKernelGGL((attention_kernel<32, RaggedDesc>), grid, block, 0, stream, a2, rd);
-                break;
-            case 64:
-                if (dma) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedDesc>), grid, block, 0, stream, a2, rd);
-                else hipLaunchKernelGGL((attention_kernel<64, RaggedDesc>), grid, block, 0, stream, a2, rd);
-                break;
-            default: return OG_E_SHAPE;
-        }
-    } else {          // uniform batch: no descriptor in the kernarg segment (og_common.h: RaggedNone)
-        switch (a.dh) {
-            case 16: hipLaunchKernelGGL((attention_kernel<16, RaggedNone>), grid, block, 0, stream, a2, RaggedNone{}); break;
-            case 128: hipLaunchKernelGGL((attention_kernel<128, RaggedNone>), grid, block, 0, stream, a2, RaggedNone{}); break;      // register-staged kernel, generic in the head size
-            case 32:
-                if (dma) hipLaunchKernelGGL((attention_dma_kernel<32, RaggedNone>), grid, block, 0, stream, a2, RaggedNone{});
-                else hipLaunchKernelGGL((attention_kernel<32, RaggedNone>), grid, block, 0, stream, a2, RaggedNone{});
-                break;
-            case 64:
-                if (dma) hipLaunchKernelGGL((attention_dma_kernel<64, RaggedNone>), grid, block, 0, stream, a2, RaggedNone{});
-                else hipLaunchKernelGGL((attention_kernel<64, RaggedNone>), grid, block, 0, stream, a2, RaggedNone{});
-                break;
-            default: return OG_E_SHAPE;
-        }
-    }
-    return og_launch_status();
+    };
+    return a.rag ? launch(*a.rag) : launch(RaggedNone{});
 }
 
 #if OG_ATTN_TRACE & 1
@@ -2227,6 +2185,6 @@ extern "C" int og_attention(const void* qh, const void* ql, int64_t ldq, const v
     a.nq[0] = nq; a.nk[0] = nk;
     a.q_base[1] = a.q_step[1] = a.kv_base[1] = a.kv_step[1] = 0; a.nq[1] = a.nk[1] = 0;
     // experiments (scripts/bench_attention.py): OG_ATTN_MX_SV=<sv> declares that `vl` holds the 8-bit rows of the MX form (og_common.h: AttnArgs::mx)
-    if (const char* e = getenv("OG_ATTN_MX_SV")) { a.mx = 1; a.mx_sv = atoi(e); }
+    if (int sv; og_knob_attn_mx_sv(&sv)) { a.mx = 1; a.mx_sv = sv; }
     return og_launch_attention(a, (hipStream_t)stream);
 }

@@ -1175,15 +1175,20 @@ int og_launch_merge_f16_hl(const void* in, int64_t rows, int cols, int64_t ldi, 
     return og_launch_status();
 }
 
-// A row-split launch (GemmHArgs::split_row) must end up on the second-generation 256-tile kernel: same conditions as the launcher's.
+// The 256-tile kernels take a launch whose `blocks` large tiles still give (nearly) every CU one (OG_GEMM_TILE=128 / 256 forces), ...
+static bool gemm_big_tile_allowed(const GemmHArgs& a, int64_t blocks) {
+    const int force = og_knob_gemm_tile();
+    return !a.alpha && !a.Ct && (force == 256 ? a.N >= BIG : ((a.N % BIG == 0 || a.batch > 1) && blocks >= 192 && force != 128));
+}
+// ... and the second-generation one those of a single plain problem.  The one rule of the launcher AND of og_gemm_f16x3_row_split_ok.
+static bool gemm_big2_allowed(const GemmHArgs& a, int64_t blocks) { return gemm_big_tile_allowed(a, blocks) && og_knob_gemm_big2() && a.batch <= 1 && !a.rag; }
+
+// A row-split launch (GemmHArgs::split_row) must end up on the second-generation 256-tile kernel, with the blocks it really computes.
 bool og_gemm_f16x3_row_split_ok(const GemmHArgs& a) {
     if (a.split_row <= 0 || a.split_row >= a.M || a.split_row % BIG || a.split_n <= 0 || a.split_n >= a.N || a.split_n % BIG) return false;
-    if (a.M % BIG || a.N % BIG || a.batch > 1 || a.rag || a.alpha || a.Ct || a.C32 || !a.Ch) return false;
-    static const int force = [] { const char* e = getenv("OG_GEMM_TILE"); return e ? atoi(e) : 0; }();
-    static const bool big2 = [] { const char* e = getenv("OG_GEMM_BIG2"); return !e || atoi(e) != 0; }();
-    static const bool on = [] { const char* e = getenv("OG_GEMM_ROW_SPLIT"); return !e || atoi(e) != 0; }();      // experiments: 0 = two launches
+    if (a.M % BIG || a.N % BIG || a.C32 || !a.Ch) return false;
     const int64_t blocks = (int64_t)(a.split_row / BIG) * (a.split_n / BIG) + (int64_t)((a.M - a.split_row) / BIG) * (a.N / BIG);
-    return on && big2 && force != 128 && blocks >= 192;
+    return og_knob_gemm_row_split() && blocks >= 192 && gemm_big2_allowed(a, blocks);
 }
 
 int og_launch_gemm_f16x3(const GemmHArgs& a, hipStream_t stream) {
@@ -1212,35 +1217,31 @@ int og_launch_gemm_f16x3(const GemmHArgs& a, hipStream_t stream) {
     g.inv_scale = (float)(1.0 / (double)a.scale);
     if (a.rag && !a.ct_rag && nz != a.rag->B) return OG_E_INVALID;
     g.rag = nullptr;
-    static const int force = [] { const char* e = getenv("OG_GEMM_TILE"); return e ? atoi(e) : 0; }();   // experiments: 128 / 256
     // The per-pair descriptor travels by value in the kernarg segment ONLY for ragged launches (og_common.h: RaggedNone).
     auto launch = [&](auto rd) -> int {
         using RD = decltype(rd);
         {   // large tiles when they still give (nearly) every CU a block
             const int tiles_m = (a.M + BIG - 1) / BIG, tiles_n = (a.N + BIG - 1) / BIG;
-            const bool fits = (a.N % BIG == 0 || nz > 1) && (int64_t)tiles_m * tiles_n * nz >= 192 && !a.alpha && !a.Ct;
-            if (force == 256 ? (a.N >= BIG && !a.alpha && !a.Ct) : (fits && force != 128)) {
+            const int64_t blocks = (int64_t)tiles_m * tiles_n * nz;
+            if (gemm_big_tile_allowed(a, blocks)) {
                 const int tiles_m8 = (tiles_m + 7) / 8 * 8;
-                static const bool big2 = [] { const char* e = getenv("OG_GEMM_BIG2"); return !e || atoi(e) != 0; }();   // experiments: 0 = first generation
-                if (big2 && nz == 1 && !a.rag) {
-                    const bool whole = g.M % 256 == 0 && g.N % 256 == 0 && g.Ch && !g.C32;      // every tile inside, split-f16 output only
-                    static const bool fast_epi = [] { const char* e = getenv("OG_GEMM_FAST_EPI"); return !e || atoi(e) != 0; }();   // experiments
+                if (gemm_big2_allowed(a, blocks)) {
+                    const bool whole = g.M % 256 == 0 && g.N % 256 == 0 && g.Ch && !g.C32 && og_knob_gemm_fast_epi();      // every tile inside, split-f16 output only (OG_GEMM_FAST_EPI=0: experiments)
                     const dim3 grid2(tiles_m8 * tiles_n), block2(512);
                     // the epilogue arithmetic as a compile-time mode where the launch is one of the GNN's four forms (OG_GEMM_SPEC_EPI=0: experiments)
-                    static const bool spec_epi = [] { const char* e = getenv("OG_GEMM_SPEC_EPI"); return !e || atoi(e) != 0; }();
                     int em = OG_EM_RUNTIME;
-                    if (spec_epi && !g.alpha) {
+                    if (og_knob_gemm_spec_epi() && !g.alpha) {
                         if (!g.res && !g.res_hl) em = g.relu ? OG_EM_RELU : OG_EM_NONE;
                         else if (!g.relu && g.res_hl) em = OG_EM_RES_HL;      // (an fp32 residual -- one launch per step -- stays on the run-time form:
                                                                               //  its 32 prefetched residual registers spill in a specialised kernel)
                     }
 #define OG_BIG2(EPI_, EM_) hipLaunchKernelGGL((gemm_nt_f16x3_big2_kernel<EPI_, EM_>), grid2, block2, 0, stream, g, tiles_m, tiles_n)
-                    if (whole && fast_epi && g.c_hl) {
+                    if (whole && g.c_hl) {
                         if (em == OG_EM_RELU) OG_BIG2(1, OG_EM_RELU);
                         else if (em == OG_EM_RES_HL) OG_BIG2(1, OG_EM_RES_HL);
                         else if (em == OG_EM_NONE) OG_BIG2(1, OG_EM_NONE);
                         else OG_BIG2(1, OG_EM_RUNTIME);
-                    } else if (whole && fast_epi && g.Cl) {
+                    } else if (whole && g.Cl) {
                         if (em == OG_EM_NONE) OG_BIG2(2, OG_EM_NONE);
                         else OG_BIG2(2, OG_EM_RUNTIME);
                     } else OG_BIG2(0, OG_EM_RUNTIME);
@@ -1256,8 +1257,7 @@ int og_launch_gemm_f16x3(const GemmHArgs& a, hipStream_t stream) {
         if (a.N > 64) {
             const int tiles_n = (a.N + 127) / 128;
             if constexpr (std::is_same<RD, RaggedNone>::value) {
-                static const bool spec128 = [] { const char* e = getenv("OG_GEMM_SPEC_EPI"); return !e || atoi(e) != 0; }();
-                const bool whole = spec128 && nz == 1 && g.M % TOK == 0 && g.N % 128 == 0 && g.Ch && !g.C32 && !g.Ct && !g.alpha && !g.res;
+                const bool whole = og_knob_gemm_spec_epi() && nz == 1 && g.M % TOK == 0 && g.N % 128 == 0 && g.Ch && !g.C32 && !g.Ct && !g.alpha && !g.res;
                 if (whole) {
                     const dim3 grid(tiles_m8 * tiles_n), block(256);
 #define OG_T128(EPI_, EM_) hipLaunchKernelGGL((gemm_nt_f16x3_kernel<128, 2, RD, EPI_, EM_>), grid, block, 0, stream, g, tiles_m, tiles_n, rd)
@@ -1337,27 +1337,27 @@ extern "C" int og_split_f16_hl(const float* x, int64_t rows, int32_t cols, int64
     return og_launch_split_f16_hl(x, rows, cols, ldx, out, ldo, (hipStream_t)stream);
 }
 
-extern "C" int og_gemm_nt_f16x3(const void* A, int64_t lda, const void* B, int64_t ldb, int32_t M, int32_t N, int32_t K,
-                                float scale, const float* bias, int32_t relu, const float* res, int64_t ldr, float* C32, int64_t ldc,
-                                void* Ch, void* Cl, int64_t ldch, int32_t c_hl, void* stream) {
+// the two stand-alone entries: one of the two residual forms each
+static int gemm_entry(const void* A, int64_t lda, const void* B, int64_t ldb, int32_t M, int32_t N, int32_t K, float scale, const float* bias, int32_t relu,
+                      const float* res, int64_t ldr, const void* res_hl, int64_t ldrh, float* C32, int64_t ldc, void* Ch, void* Cl, int64_t ldch, int32_t c_hl, void* stream) {
     og_clear_status();
     GemmHArgs g{};
     g.A = (const _Float16*)A; g.lda = lda; g.B = (const _Float16*)B; g.ldb = ldb;
-    g.M = M; g.N = N; g.K = K; g.scale = scale; g.bias = bias; g.relu = relu; g.res = res; g.ldr = ldr;
+    g.M = M; g.N = N; g.K = K; g.scale = scale; g.bias = bias; g.relu = relu; g.res = res; g.ldr = ldr; g.res_hl = (const _Float16*)res_hl; g.ldrh = ldrh;
     g.C32 = C32; g.ldc = ldc; g.Ch = (_Float16*)Ch; g.Cl = c_hl ? (Ch ? (_Float16*)Ch + 32 : nullptr) : (_Float16*)Cl;
     g.ldch = ldch; g.c_hl = c_hl ? 1 : 0;
     return og_launch_gemm_f16x3(g, (hipStream_t)stream);
+}
+
+extern "C" int og_gemm_nt_f16x3(const void* A, int64_t lda, const void* B, int64_t ldb, int32_t M, int32_t N, int32_t K,
+                                float scale, const float* bias, int32_t relu, const float* res, int64_t ldr, float* C32, int64_t ldc,
+                                void* Ch, void* Cl, int64_t ldch, int32_t c_hl, void* stream) {
+    return gemm_entry(A, lda, B, ldb, M, N, K, scale, bias, relu, res, ldr, nullptr, 0, C32, ldc, Ch, Cl, ldch, c_hl, stream);
 }
 
 // the fc.3 form of the GNN: the residual arrives as hl32 rows (og_forward keeps the residual stream that way)
 extern "C" int og_gemm_nt_f16x3_reshl(const void* A, int64_t lda, const void* B, int64_t ldb, int32_t M, int32_t N, int32_t K,
                                       float scale, const float* bias, int32_t relu, const void* res_hl, int64_t ldrh, float* C32, int64_t ldc,
                                       void* Ch, void* Cl, int64_t ldch, int32_t c_hl, void* stream) {
-    og_clear_status();
-    GemmHArgs g{};
-    g.A = (const _Float16*)A; g.lda = lda; g.B = (const _Float16*)B; g.ldb = ldb;
-    g.M = M; g.N = N; g.K = K; g.scale = scale; g.bias = bias; g.relu = relu; g.res_hl = (const _Float16*)res_hl; g.ldrh = ldrh;
-    g.C32 = C32; g.ldc = ldc; g.Ch = (_Float16*)Ch; g.Cl = c_hl ? (Ch ? (_Float16*)Ch + 32 : nullptr) : (_Float16*)Cl;
-    g.ldch = ldch; g.c_hl = c_hl ? 1 : 0;
-    return og_launch_gemm_f16x3(g, (hipStream_t)stream);
+    return gemm_entry(A, lda, B, ldb, M, N, K, scale, bias, relu, nullptr, 0, res_hl, ldrh, C32, ldc, Ch, Cl, ldch, c_hl, stream);
 }

@@ -298,9 +298,8 @@ int og_launch_gemm(const GemmArgs& a, hipStream_t stream) {
     // (profiles/r05_v_*): training step 39.3 -> 32.3 ms at 4 pairs, 81.4 -> 75.0 ms at 16 pairs (512 ... 1536 wide workgroups per launch), the
     // encoder convs of the inference path 0.093 -> 0.068 ms at C2; 64 x 64 below 1024 workgroups: a 4096 x 256 x 256 launch 19.0 -> 12.3 us, the
     // training step 28.9 -> 26.0 ms at 4 pairs, no change at 16 (profiles/r05_x_*).
-    static const int force_bn = [] { const char* e = getenv("OG_GEMM_F32_BN"); return e ? atoi(e) : 0; }();
-    static const int force_bm = [] { const char* e = getenv("OG_GEMM_F32_BM"); return e ? atoi(e) : 0; }();
-    static const int64_t short_below = [] { const char* e = getenv("OG_GEMM_F32_SHORT_BELOW"); return e ? atoll(e) : 1024LL; }();
+    const int force_bn = og_knob_gemm_f32_bn(), force_bm = og_knob_gemm_f32_bm();
+    const int64_t short_below = og_knob_gemm_f32_short_below();
     const bool narrow = a.N <= 64 || force_bn != 128;
     const int64_t wgs_tall = (int64_t)((a.M + 127) / 128) * a.batch * ((a.N + 63) / 64);
     const bool shortt = narrow && (force_bm == 64 ? true : force_bm == 128 ? false : wgs_tall < short_below);

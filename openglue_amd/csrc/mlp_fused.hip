@@ -1346,10 +1346,7 @@ bool og_mlp_fused_supported(int D) { return D == 256 || D == 128; }
 
 size_t og_mlp_stream_bytes(int D) { return og_mlp_fused_supported(D) ? (size_t)6 * D * D * 4 : 0; }      // 4D^2 (W0') + 2D^2 (W3') (hi, lo) pairs
 
-bool og_mlp_fused_enabled(int D) {
-    static const bool on = [] { const char* e = getenv("OG_MLP_FUSED"); return !e || atoi(e) != 0; }();   // experiments: 0 = fc.0 and fc.3 as two GEMM launches
-    return on && og_mlp_fused_supported(D);
-}
+bool og_mlp_fused_enabled(int D) { return og_knob_mlp_fused() && og_mlp_fused_supported(D); }
 
 // Fragment-major weight stream of mlp_fused_kernel.  W0 [2D][2D], W3 [D][2D] row-major double (already folded), written as (hi, lo)
 // halves of S0 w / S3 w (power-of-two pre-scales, 256 unless a weight would leave binary16).  256-d: 48 stages of 32 fragments (1 KiB = 64 lanes x 8 halves; a lo fragment
@@ -1401,11 +1398,7 @@ bool og_pack_mlp_stream(int D, const double* W0, const double* W3, void* out, do
 
 // Few token rows: 32-token workgroups whose waves split the hidden dimension (mlp_small_kernel).  Up to 8192 rows = 256 workgroups, one
 // round of the chip; above that the 128-token tiles of mlp_fused_kernel stream the weights four times less often.  OG_MLP_SMALL=0 / 1 forces.
-bool og_mlp_small_wanted(int M) {
-    static const int mode = [] { const char* e = getenv("OG_MLP_SMALL"); return e ? atoi(e) : -1; }();
-    if (mode >= 0) return mode != 0;
-    return M <= 8192;
-}
+bool og_mlp_small_wanted(int M) { return og_knob_mlp_small() >= 0 ? og_knob_mlp_small() != 0 : M <= 8192; }
 
 int og_launch_mlp_fused(const MlpFusedArgs& a, int D, hipStream_t stream) {
     if (!a.XO || !a.wstream || !a.b0 || !a.b3 || a.M <= 0) return OG_E_INVALID;
@@ -1491,8 +1484,7 @@ int og_launch_proj_small(const _Float16* X, int64_t ld, int M, int K, const char
     // streams 256 KB of weights instead of the whole matrix (the per-CU weight stream is what bounds these kernels).
     const int tiles = (M + SM_T - 1) / SM_T, nblk = (a1 - a0) > (b1 - b0) ? (a1 - a0) : (b1 - b0);
     int parts = 1, bpp = nblk > 0 ? nblk : 1;
-    static const bool split_on = [] { const char* e = getenv("OG_PROJ_PARTS"); return !(e && e[0] == '0'); }();      // OG_PROJ_PARTS=0: one workgroup per token tile
-    if (split_on && nblk > 8 && tiles * ((nblk + 7) / 8) <= 256) { parts = (nblk + 7) / 8; bpp = 8; }
+    if (og_knob_proj_parts() &&nblk > 8 && tiles * ((nblk + 7) / 8) <= 256) { parts = (nblk + 7) / 8; bpp = 8; }
     if (nblk > 24) { parts = (nblk + 7) / 8; bpp = 8; }          // a workgroup covers at most 3 blocks per wave: wider ranges are always dealt out
     ProjSmallArgs g{X, ld, M, wstream, bias, scale_dev, Ch, Cl, ldc, split_row, a0, a1, b0, b1, parts, bpp};
     if (K == 256) hipLaunchKernelGGL(proj_small_kernel<256>, dim3(tiles * parts), dim3(512), 0, stream, g);
@@ -1528,6 +1520,10 @@ bool og_pack_proj_stream_big(int N, int K, const double* W, void* out, double S)
     return ok;
 }
 
+// og_forward: few rows (<= 8192 per launch, the single-pair regime) take proj_small_kernel, 32-token workgroups over a fragment-major copy of the
+// matrix -- 17.5 us per launch of the 128-token tile GEMM otherwise, 36 launches per step.  OG_PROJ_SMALL=0 / 1 forces.
+bool og_proj_small_wanted(int64_t R) { return og_knob_proj_small() >= 0 ? og_knob_proj_small() != 0 : R <= 8192; }
+
 // og_forward: launches of more than 8192 rows take proj_stream_kernel at K = 128 (OG_PROJ_STREAM=0 / 1 forces for both widths).  Measured in one
 // gpurun call (profiles/r05_c_proj_micro.log, r05_b_bench_proj_stream_ab.jsonl): K = 128 -- self 37.8 us against 52.6 for the 128-token tile GEMM,
 // cross 29.2 / 40.7, kv 16.8 / 21.3; C4 13.29 -> 13.12 ms, S128 12.27 -> 12.12 ms per step.  K = 256 -- self 102 us against 104.5 for the 256-tile
@@ -1536,7 +1532,7 @@ bool og_pack_proj_stream_big(int N, int K, const double* W, void* out, double S)
 // kernel takes those launches only (95 against 104.5 us in the micro-benchmark), the tile GEMMs the cross / kv forms.
 // (og_forward packs the batch stream for K = 128 only -- api.hip: packed_layout -- so forcing the K = 256 form reaches the stage entry og_proj_block alone)
 bool og_proj_stream_wanted(int M, int K, bool full) {
-    static const int mode = [] { const char* e = getenv("OG_PROJ_STREAM"); return e ? atoi(e) : -1; }();
+    const int mode = og_knob_proj_stream();
     if (mode == 2) return M > 8192 && (K == 128 || full);
     if (mode >= 0) return mode != 0 && M > 0;
     return M > 8192 && K == 128;
@@ -1581,7 +1577,7 @@ extern "C" int og_proj_block(const void* x_rows, int64_t ld, int32_t M, int32_t 
     if (!og_proj_stream_bytes(N, K)) return OG_E_SHAPE;
     // batches: the 128-token kernel (its stream sits behind the small one, located by N: ABI v10) when the ranges are whole 128-channel groups
     // (the stage entry of BOTH kernels: above 8192 rows it runs proj_stream_kernel at either width, whatever og_forward prefers)
-    static const int ps_mode = [] { const char* e = getenv("OG_PROJ_STREAM"); return e ? atoi(e) : -1; }();
+    const int ps_mode = og_knob_proj_stream();
     // 256-d batches whose planes are as wide as the matrix (ldy == N, og_forward's own geometry) and whose ranges are whole 256-column slabs: the
     // weight-stationary kernel og_forward runs there (proj_wstat.hip; it reads the small-batch stream)
     if (ps_mode < 0 && og_proj_wstat_wanted(M, K) && ldy == N && !(a0 % 8) && !(a1 % 8) && !(b0 % 8) && !(b1 % 8) && !(ldy & 7) &&

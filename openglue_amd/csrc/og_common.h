@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/openglue_amd.h"
+#include "og_knobs.h"      // the OG_* environment knobs: one accessor each
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -208,6 +209,7 @@ bool og_mlp_small_wanted(int M);
 // the q / k / v projections for few token rows (mlp_fused.hip: proj_small_kernel), a fragment-major copy of the packed matrix
 size_t og_proj_stream_bytes(int N, int K);
 bool og_pack_proj_stream(int N, int K, const double* W, void* out, double S);
+bool og_proj_small_wanted(int64_t R);                     // og_forward's choice: at most 8192 rows per launch (OG_PROJ_SMALL forces)
 // ... and for batches (mlp_fused.hip: proj_stream_kernel, 128-token workgroups, x fragments in registers, the weights through an LDS ring)
 size_t og_proj_stream_big_bytes(int N, int K);
 bool og_pack_proj_stream_big(int N, int K, const double* W, void* out, double S);

@@ -35,6 +35,31 @@ inline SinkhornGeom sk_geom(int n) {
     if (n <= 4096) return {4, 4};
     return {8, 4};               // <= 8192
 }
+// f(CPL, RG, WPR), as integral constants, for the sweep geometry g: the one list of the six instantiated <CPL, RG, WPR> forms
+template <class F>
+void sk_with_geom(const SinkhornGeom& g, F&& f) {
+#define OG_SKG(CPL_, RG_, WPR_) f(std::integral_constant<int, CPL_>{}, std::integral_constant<int, RG_>{}, std::integral_constant<int, WPR_>{})
+    if (g.CPL == 1) OG_SKG(1, 4, 1);
+    else if (g.CPL == 2) OG_SKG(2, 4, 1);
+    else if (g.CPL == 8) OG_SKG(8, 1, 4);
+    else if (g.WPR == 1) OG_SKG(4, 2, 1);
+    else if (g.WPR == 2) OG_SKG(4, 2, 2);
+    else OG_SKG(4, 2, 4);
+#undef OG_SKG
+}
+
+// log marginals of an m x n problem with dustbins (superglue.py:96-101): norm = -log(m + n); the dustbin entries add log(n) / log(m) in fp32
+struct SkMarginals {
+    float norm, la, lb, la_bin, lb_bin;
+    SkMarginals(int m, int n)          // log_a[-1] += log(n) in fp32 (superglue.py:100)
+        : norm((float)-log((double)m + (double)n)), la(norm), lb(norm), la_bin(norm + (float)log((double)n)), lb_bin(norm + (float)log((double)m)) {}
+};
+
+// Floats of the streaming workspace of B pairs: u, the v ping-pong and the four flag words (sk_dual_floats: zeroed together at the top of
+// every call), then the two arrays of column partials.  sk_layout carves exactly these; the resident exchange area follows them.
+inline int64_t sk_dual_floats(int B, int m, int n) { return (int64_t)B * (og_round_up(m + 1, 4) + 2 * og_round_up(n + 1, 4)) + 4; }
+inline int64_t sk_partial_floats(int B, int m, int n) { return (int64_t)B * ((m + SK_ROWS - 1) / SK_ROWS) * og_round_up(n, 4); }
+inline int64_t sk_stream_floats(int B, int m, int n) { return sk_dual_floats(B, m, n) + 2 * sk_partial_floats(B, m, n); }
 
 struct SinkhornWs {
     float* u;       // [B][ldu]
@@ -52,13 +77,12 @@ static SinkhornWs sk_layout(void* ws, int B, int m, int n) {
     w.ldu = (int)og_round_up(m + 1, 4);
     w.ldv = (int)og_round_up(n + 1, 4);
     w.ldp = (int)og_round_up(n, 4);
-    float* p = (float*)ws;
-    w.u = p; p += (int64_t)B * w.ldu;
-    w.v[0] = p; p += (int64_t)B * w.ldv;
-    w.v[1] = p; p += (int64_t)B * w.ldv;
-    w.flags = (unsigned*)p; p += 4;
-    w.pm = p; p += (int64_t)B * w.RB * w.ldp;
-    w.ps = p;
+    w.u = (float*)ws;
+    w.v[0] = w.u + (int64_t)B * w.ldu;
+    w.v[1] = w.v[0] + (int64_t)B * w.ldv;
+    w.flags = (unsigned*)(w.v[1] + (int64_t)B * w.ldv);
+    w.pm = w.u + sk_dual_floats(B, m, n);
+    w.ps = w.pm + sk_partial_floats(B, m, n);
     return w;
 }
 
@@ -769,21 +793,24 @@ __global__ __launch_bounds__(1024) void sinkhorn_fallback_kernel(const float* __
 
 extern "C" size_t og_sinkhorn_workspace_bytes(int32_t batch, int32_t m, int32_t n) {
     if (batch <= 0 || m <= 0 || n <= 0 || n > 8192) return 0;
-    const int64_t RB = (m + SK_ROWS - 1) / SK_ROWS;
-    const int64_t ldu = og_round_up(m + 1, 4), ldv = og_round_up(n + 1, 4), ldp = og_round_up(n, 4);
-    const int64_t floats = (int64_t)batch * (ldu + 2 * ldv) + 4 + 2 * (int64_t)batch * RB * ldp;
     // + the exchange area of the on-chip-resident iteration kernel (sinkhorn_resident.hip), 256-byte aligned
-    return (size_t)og_round_up(floats * (int64_t)sizeof(float), 256) + og_sinkhorn_resident_ws_bytes(batch, m, n);
+    return (size_t)og_round_up(sk_stream_floats(batch, m, n) * (int64_t)sizeof(float), 256) + og_sinkhorn_resident_ws_bytes(batch, m, n);
 }
 
-static inline void* sk_resident_ws(void* ws, int B, int m, int n) {
-    const int64_t RB = (m + SK_ROWS - 1) / SK_ROWS;
-    const int64_t ldu = og_round_up(m + 1, 4), ldv = og_round_up(n + 1, 4), ldp = og_round_up(n, 4);
-    const int64_t floats = (int64_t)B * (ldu + 2 * ldv) + 4 + 2 * (int64_t)B * RB * ldp;
-    return (char*)ws + og_round_up(floats * (int64_t)sizeof(float), 256);
-}
+static inline void* sk_resident_ws(void* ws, int B, int m, int n) { return (char*)ws + og_round_up(sk_stream_floats(B, m, n) * (int64_t)sizeof(float), 256); }
 
 namespace {
+// The on-chip-resident schedule runs iterations 2 .. iters: more than one iteration, not switched off (OG_SINKHORN_ROBUST=1,
+// OG_SINKHORN_RESIDENT=0) and a batch the resident kernel takes; for a ragged batch m, n are the maxima.  One rule for sinkhorn_run and
+// for what og_sinkhorn_schedule / og_sinkhorn_schedule_ragged report.
+template <class RD>
+bool sk_resident_enabled(const RD& rd, int B, int m, int n, int iters) {
+    if (og_knob_sinkhorn_robust() || iters <= 1) return false;
+    const int mode = og_knob_sinkhorn_resident();
+    if constexpr (std::is_same<RD, RaggedNone>::value) return og_sinkhorn_resident_wanted(B, m, n, mode);
+    else return og_sinkhorn_resident_ws_bytes(B, m, n) > 0 && og_sinkhorn_resident_ragged_wanted(rd, mode);
+}
+
 // RD = RaggedDesc (per-pair sizes by value in the kernarg segment) or RaggedNone (uniform batch: nothing; og_common.h)
 template <class RD>
 int sinkhorn_run(const float* S, int64_t lds, const float* zdev, float dustbin, int B, int m, int n, int iters, float reg,
@@ -793,23 +820,15 @@ int sinkhorn_run(const float* S, int64_t lds, const float* zdev, float dustbin, 
     if ((lds & 3) || ((uintptr_t)S & 15) || ((uintptr_t)workspace & 15)) return OG_E_ALIGN;
     const SinkhornWs w = sk_layout(workspace, B, m, n);
     const float inv_reg = 1.f / reg;
-    const double norm = -log((double)m + (double)n);
-    const float la = (float)norm, lb = (float)norm;
-    const float la_bin = (float)norm + (float)log((double)n);   // log_a[-1] += log(n) in fp32 (superglue.py:100)
-    const float lb_bin = (float)norm + (float)log((double)m);
+    const SkMarginals mg(m, n);
+    const float la = mg.la, lb = mg.lb, la_bin = mg.la_bin, lb_bin = mg.lb_bin;
     // u = v = 0 (optimal_transport.py:22)
-    hipError_t e = hipMemsetAsync(w.u, 0, sizeof(float) * ((size_t)B * (w.ldu + 2 * (size_t)w.ldv) + 4), st);      // ... and the flags behind them
+    hipError_t e = hipMemsetAsync(w.u, 0, sizeof(float) * (size_t)sk_dual_floats(B, m, n), st);      // ... and the flags behind them
     if (e != hipSuccess) return (int)e;
     const SinkhornGeom g = sk_geom(n);
     int cur = 0;
-    static const bool robust_only = [] { const char* e = getenv("OG_SINKHORN_ROBUST"); return e && atoi(e) != 0; }();   // experiments
-    // 0: streaming kernels only; 1 (default): on-chip-resident iterations when the batch is co-resident and big enough to pay
-    // off; 2: whenever it is co-resident (tests)
-    const char* rm_env = getenv("OG_SINKHORN_RESIDENT");          // read per call: the parity tests switch it
-    const int resident_mode = rm_env ? atoi(rm_env) : 1;
-    bool resident = !robust_only && iters > 1;
-    if constexpr (std::is_same<RD, RaggedNone>::value) resident = resident && og_sinkhorn_resident_wanted(B, m, n, resident_mode);
-    else resident = resident && og_sinkhorn_resident_ws_bytes(B, m, n) > 0 && og_sinkhorn_resident_ragged_wanted(rd, resident_mode);
+    const bool robust_only = og_knob_sinkhorn_robust();
+    const bool resident = sk_resident_enabled(rd, B, m, n, iters);
     // Geometry of the dual-stabilised streaming sweeps (uniform batches): the largest 32 / 64 / 128 rows per workgroup that still gives
     // >= 512 workgroups -- half the column partials to write and merge per doubling (2048 columns x 32 pairs: 11.6 -> 9.2 ms per 100
     // iterations at 128 rows with streaming loads; 4096 x 8 pairs: 11.4 -> 9.5 at 64; below 512 workgroups the chip runs dry: 16.6 ms at
@@ -821,15 +840,14 @@ int sinkhorn_run(const float* S, int64_t lds, const float* zdev, float dustbin, 
             if ((int64_t)((m + r - 1) / r) * B >= 512) fast_rows = r;
         fast_nt = (int64_t)B * m * lds * (int64_t)sizeof(float) > ((int64_t)256 << 20);
     }
-    { const char* e = getenv("OG_SK_FAST_ROWS"); if (e && (atoi(e) == 32 || atoi(e) == 64 || atoi(e) == 128)) fast_rows = atoi(e); }
-    { const char* e = getenv("OG_SK_FAST_NT"); if (e) fast_nt = atoi(e) != 0; }
+    if (const int r = og_knob_sk_fast_rows(); r == 32 || r == 64 || r == 128) fast_rows = r;
+    if (const int nt = og_knob_sk_fast_nt(); nt >= 0) fast_nt = nt;
     for (int it = 0; it < iters; ++it) {
         const float* vin = w.v[cur];
         if (it > 0 && resident) {         // iterations 2 .. iters in ONE launch, S read once (sinkhorn_resident.hip)
             unsigned* status = w.flags + 1;          // zeroed with u, v, flags[0] at the top of every call
             void* xws = sk_resident_ws(workspace, B, m, n);
-            const char* ft = getenv("OG_SINKHORN_FORCE_TIMEOUT");     // tests: behave as if a peer workgroup never arrived
-            if (ft && atoi(ft) != 0) {
+            if (og_knob_sinkhorn_force_timeout()) {      // tests: behave as if a peer workgroup never arrived
                 e = hipMemsetAsync(status, 1, sizeof(unsigned), st);
                 if (e != hipSuccess) return (int)e;
             } else {
@@ -851,29 +869,19 @@ int sinkhorn_run(const float* S, int64_t lds, const float* zdev, float dustbin, 
         if (it > 0 && !robust_only) {     // dual-stabilised form: valid once one max-subtracted iteration has been done
             const float is = it == 1 ? LOG2E : 1.f, os = it == iters - 1 ? LN2 : 1.f;     // duals stay in base 2 in between
             const int rows = (std::is_same<RD, RaggedNone>::value && g.WPR > 1) ? fast_rows : SK_ROWS, RBf = (m + rows - 1) / rows;
-            if (g.CPL == 1) launch_sweep_fast<1, 4, 1>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd, is, os, rows, fast_nt);
-            else if (g.CPL == 2) launch_sweep_fast<2, 4, 1>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd, is, os, rows, fast_nt);
-            else if (g.CPL == 8) launch_sweep_fast<8, 1, 4>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd, is, os, rows, fast_nt);
-            else if (g.WPR == 1) launch_sweep_fast<4, 2, 1>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd, is, os, rows, fast_nt);
-            else if (g.WPR == 2) launch_sweep_fast<4, 2, 2>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd, is, os, rows, fast_nt);
-            else launch_sweep_fast<4, 2, 4>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd, is, os, rows, fast_nt);
+            sk_with_geom(g, [&](auto c, auto r, auto p) { launch_sweep_fast<c(), r(), p()>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd, is, os, rows, fast_nt); });
             hipLaunchKernelGGL(sinkhorn_combine_fast_kernel<RD>, dim3((n + 1 + 255) / 256, B), dim3(256), 0, st, m, n, zdev, dustbin,
                                inv_reg, la_bin, lb, lb_bin, w.v[cur], w.v[cur ^ 1], w.ldv, w.u, w.ldu, w.ps, w.ldp, RBf, is, os, rows, rd);
             cur ^= 1;
             continue;
         }
-        if (g.CPL == 1) launch_sweep<1, 4, 1>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.CPL == 2) launch_sweep<2, 4, 1>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.CPL == 8) launch_sweep<8, 1, 4>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.WPR == 1) launch_sweep<4, 2, 1>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.WPR == 2) launch_sweep<4, 2, 2>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd);
-        else launch_sweep<4, 2, 4>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd);
+        sk_with_geom(g, [&](auto c, auto r, auto p) { launch_sweep<c(), r(), p()>(S, lds, B, m, n, zdev, dustbin, inv_reg, la, vin, w, st, rd); });
         hipLaunchKernelGGL(sinkhorn_combine_kernel<RD>, dim3((n + 1 + 255) / 256, B), dim3(256), 0, st, m, n, zdev, dustbin, inv_reg, la_bin,
                            lb, lb_bin, w.v[cur], w.v[cur ^ 1], w.ldv, w.u, w.ldu, w.pm, w.ps, w.ldp, w.RB, rd);
         cur ^= 1;
     }
     hipLaunchKernelGGL(sinkhorn_scores_kernel<RD>, dim3((m + 1 + 3) / 4, B), dim3(256), 0, st, S, lds, m, n, zdev, dustbin, inv_reg,
-                       (float)norm, w.u, w.ldu, w.v[cur], w.ldv, scores, (int64_t)m * lds, rd, row_best ? *row_best : RowBest{nullptr, nullptr, 0}, w.flags);
+                       mg.norm, w.u, w.ldu, w.v[cur], w.ldv, scores, (int64_t)m * lds, rd, row_best ? *row_best : RowBest{nullptr, nullptr, 0}, w.flags);
     return og_launch_status();
 }
 }  // namespace
@@ -885,9 +893,7 @@ int og_launch_sinkhorn_trajectory(const float* S, int64_t lds, const float* dust
     if (n > 8192) return OG_E_SHAPE;
     SinkhornWs w = sk_layout(workspace, B, m, n);
     const float inv_reg = 1.f / reg;
-    const double norm = -log((double)m + (double)n);
-    const float la = (float)norm, lb = (float)norm;
-    const float la_bin = (float)norm + (float)log((double)n), lb_bin = (float)norm + (float)log((double)m);
+    const SkMarginals mg(m, n);
     // v_0 = 0 (optimal_transport.py:22) -- and the whole trajectory with it: the sweep loads v_in in groups of four columns, so for n % 4 == 1 or 2
     // it touches the gap columns (n, ldv) of v_t, which the combine never writes.  They meet -inf and contribute exp(-inf) = 0 unless they hold NaN or
     // +inf, as a recycled workspace can: then every score of the call was NaN.
@@ -899,17 +905,12 @@ int og_launch_sinkhorn_trajectory(const float* S, int64_t lds, const float* dust
         const float* vin = V + (size_t)it * B * w.ldv;
         float* vout = V + (size_t)(it + 1) * B * w.ldv;
         w.u = U + (size_t)it * B * w.ldu;                      // the sweep writes u_t of every row, the combine u_t of the dustbin row
-        if (g.CPL == 1) launch_sweep<1, 4, 1>(S, lds, B, m, n, dustbin_dev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.CPL == 2) launch_sweep<2, 4, 1>(S, lds, B, m, n, dustbin_dev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.CPL == 8) launch_sweep<8, 1, 4>(S, lds, B, m, n, dustbin_dev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.WPR == 1) launch_sweep<4, 2, 1>(S, lds, B, m, n, dustbin_dev, dustbin, inv_reg, la, vin, w, st, rd);
-        else if (g.WPR == 2) launch_sweep<4, 2, 2>(S, lds, B, m, n, dustbin_dev, dustbin, inv_reg, la, vin, w, st, rd);
-        else launch_sweep<4, 2, 4>(S, lds, B, m, n, dustbin_dev, dustbin, inv_reg, la, vin, w, st, rd);
+        sk_with_geom(g, [&](auto c, auto r, auto p) { launch_sweep<c(), r(), p()>(S, lds, B, m, n, dustbin_dev, dustbin, inv_reg, mg.la, vin, w, st, rd); });
         hipLaunchKernelGGL(sinkhorn_combine_kernel<RaggedNone>, dim3((n + 1 + 255) / 256, B), dim3(256), 0, st, m, n, dustbin_dev, dustbin,
-                           inv_reg, la_bin, lb, lb_bin, vin, vout, w.ldv, w.u, w.ldu, w.pm, w.ps, w.ldp, w.RB, rd);
+                           inv_reg, mg.la_bin, mg.lb, mg.lb_bin, vin, vout, w.ldv, w.u, w.ldu, w.pm, w.ps, w.ldp, w.RB, rd);
     }
     hipLaunchKernelGGL(sinkhorn_scores_kernel<RaggedNone>, dim3((m + 1 + 3) / 4, B), dim3(256), 0, st, S, lds, m, n, dustbin_dev, dustbin,
-                       inv_reg, (float)norm, U + (size_t)(iters - 1) * B * w.ldu, w.ldu, V + (size_t)iters * B * w.ldv, w.ldv, scores,
+                       inv_reg, mg.norm, U + (size_t)(iters - 1) * B * w.ldu, w.ldu, V + (size_t)iters * B * w.ldv, w.ldv, scores,
                        (int64_t)m * lds, rd, RowBest{nullptr, nullptr, 0}, (unsigned*)nullptr);
     return og_launch_status();
 }
@@ -924,17 +925,11 @@ int og_launch_sinkhorn(const float* S, int64_t lds, const float* zdev, float dus
 }
 
 extern "C" int og_sinkhorn_schedule(int32_t batch, int32_t m, int32_t n, int32_t iters) {
-    static const bool robust_only = [] { const char* e = getenv("OG_SINKHORN_ROBUST"); return e && atoi(e) != 0; }();
-    const char* rm_env = getenv("OG_SINKHORN_RESIDENT");
-    const int resident_mode = rm_env ? atoi(rm_env) : 1;
-    return (!robust_only && iters > 1 && og_sinkhorn_resident_wanted(batch, m, n, resident_mode)) ? og_sinkhorn_resident_rounds(batch, m, n) : 0;
+    return sk_resident_enabled(RaggedNone{}, batch, m, n, iters) ? og_sinkhorn_resident_rounds(batch, m, n) : 0;
 }
 
 extern "C" int og_sinkhorn_schedule_ragged(int32_t batch, const int32_t* lens0, const int32_t* lens1, int32_t iters) {
-    static const bool robust_only = [] { const char* e = getenv("OG_SINKHORN_ROBUST"); return e && atoi(e) != 0; }();
-    if (batch <= 0 || batch > OG_MAX_RAGGED || !lens0 || !lens1 || robust_only || iters <= 1) return 0;
-    const char* rm_env = getenv("OG_SINKHORN_RESIDENT");
-    const int resident_mode = rm_env ? atoi(rm_env) : 1;
+    if (batch <= 0 || batch > OG_MAX_RAGGED || !lens0 || !lens1) return 0;
     RaggedDesc rd{};
     rd.B = batch;
     int mmax = 0, nmax = 0;
@@ -943,7 +938,7 @@ extern "C" int og_sinkhorn_schedule_ragged(int32_t batch, const int32_t* lens0, 
         if (lens0[b] > mmax) mmax = lens0[b];
         if (lens1[b] > nmax) nmax = lens1[b];
     }
-    if (og_sinkhorn_resident_ws_bytes(batch, mmax, nmax) == 0 || !og_sinkhorn_resident_ragged_wanted(rd, resident_mode)) return 0;
+    if (!sk_resident_enabled(rd, batch, mmax, nmax, iters)) return 0;
     int launches = 0;
     if (og_launch_sinkhorn_resident_ragged(nullptr, 0, nullptr, 0.f, rd, mmax, nmax, iters - 1, 1.f, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, true, &launches)) return 0;
     return launches;

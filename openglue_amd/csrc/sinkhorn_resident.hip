@@ -902,8 +902,7 @@ int rs_rows_per_wave(int B, int m, int n, int cus) {
     if (cus < 256 || n > RS_SEG) return RS_RW;
     const RsGeom q16 = rs_geom(m, n);
     if (q16.W == 0) return RS_RW;
-    const char* e = getenv("OG_SINKHORN_FEW");                       // read per call: the tests switch it; 0 = never, 4 / 8 = that geometry when it exists, 1 = the finest
-    const int want = e ? atoi(e) : -1;
+    const int want = og_knob_sinkhorn_few();                         // read per call: the tests switch it; 0 = never, 4 / 8 = that geometry when it exists, 1 = the finest
     if (want == 0) return RS_RW;
     for (int rw = 4; rw <= 8; rw *= 2) {                             // the finest geometry that still fits ONE launch (and, by default, fills <= all CUs from <= half of them)
         if (want > 1 && want != rw) continue;
@@ -979,7 +978,7 @@ int og_launch_sinkhorn_resident(const float* S, int64_t lds, const float* zdev, 
     a.status = status;
     a.xcc = (unsigned*)((char*)xws + 256);
     a.xa = (char*)xws + 256 + RS_MAXWG * sizeof(unsigned);
-    { const char* ev = getenv("OG_SINKHORN_AGENT_SCOPE"); a.force_agent_scope = ev && atoi(ev) != 0; }       // read per call: the tests switch it
+    a.force_agent_scope = og_knob_sinkhorn_agent_scope();       // read per call: the tests switch it
     a.zdev = zdev; a.zhost = zhost; a.inv_reg = inv_reg; a.la = la; a.la_bin = la_bin; a.lb = lb; a.lb_bin = lb_bin;
     a.m = m; a.n = n; a.iters = iters;
     a.sanitize_pad = (n & 3) && !trusted_padding;
@@ -1119,7 +1118,7 @@ int og_launch_sinkhorn_resident_ragged(const float* S, int64_t lds, const float*
     a.status = status;
     a.xcc = (unsigned*)((char*)xws + 256);
     a.xa = (char*)xws + 256 + RS_MAXWG * sizeof(unsigned);
-    { const char* ev = getenv("OG_SINKHORN_AGENT_SCOPE"); a.force_agent_scope = ev && atoi(ev) != 0; }
+    a.force_agent_scope = og_knob_sinkhorn_agent_scope();
     a.zdev = zdev; a.zhost = zhost; a.inv_reg = inv_reg;
     a.m = m_max; a.n = n_max; a.iters = iters; a.local_ok = 1;
     (void)trusted_padding;

@@ -239,7 +239,7 @@ extern "C" int og_sinkhorn_backward(const float* S, int64_t lds, float dustbin, 
     if (d_dustbin && (e = hipMemsetAsync(d_dustbin, 0, sizeof(float), st)) != hipSuccess) return (int)e;
     hipLaunchKernelGGL(sk_bwd_init_kernel, dim3((m + 1 + 3) / 4, B), dim3(256), 0, st, S, lds, dustbin_dev, dustbin, inv_reg, m, n, grad_scores, w.Za,
                        w.dZ, w.lda, w.du, w.ldu, w.dv[0], w.ldv);
-    static const int rows_cap = [] { const char* e = getenv("OG_SK_BWD_ROWS_GRID"); return e && atoi(e) > 0 ? atoi(e) : 128; }();   // experiments (64 ... 512 measured: profiles/r05_ab_*)
+    const int rows_cap = og_knob_sk_bwd_rows_grid() > 0 ? og_knob_sk_bwd_rows_grid() : 128;   // experiments (64 ... 512 measured: profiles/r05_ab_*)
     const int rows_grid = (m + 1 + 3) / 4 < rows_cap ? (m + 1 + 3) / 4 : rows_cap;       // waves stride over the rows
     int cur = 0;
     for (int t = T; t >= 1; --t) {

@@ -37,25 +37,25 @@ ATTN_PARTIAL_WG = 512                  # og_common.h: OG_ATTN_PARTIAL_FLOATS / (
 
 
 def expected_instance(nz, H, dh, nq, nk, ragged=False, scratch=False):
-    """The instance og_launch_attention (attention.hip:1977-2130) launches in the default environment.  nq: the largest query count of
+    """The instance og_launch_attention launches in the default environment: attention.hip, attn_plan restated.  nq: the largest query count of
     the launch, nk: the smallest key count (nqmax / nkmin there); scratch: the caller passed partial + counters (og_forward does)."""
     rd = "RaggedDesc" if ragged else "RaggedNone"
-    grid = (nz * H + 7) // 8 * 8 * ((nq + Q_TILE - 1) // Q_TILE)        # :1999-2000
-    dma = dh in (32, 64)                                                   # :1998
-    if dma and scratch and grid <= ATTN_COUNTERS:                          # :2013 grid split
-        maxwg = 512 if dh == 32 else 256                                   # :2019
+    grid = (nz * H + 7) // 8 * 8 * ((nq + Q_TILE - 1) // Q_TILE)        # attn_plan: wgs
+    dma = dh in (32, 64)                                                   # attn_plan: dma
+    if dma and scratch and grid <= ATTN_COUNTERS:                          # grid split
+        maxwg = 512 if dh == 32 else 256                                   # maxwg
         gs = 1
-        if grid * 4 <= maxwg and (ragged or nk >= 16 * KV_TILE):          # :2021
+        if grid * 4 <= maxwg and (ragged or nk >= 16 * KV_TILE):
             gs = 4
-        elif grid * 2 <= maxwg and (ragged or nk >= 8 * KV_TILE):         # :2022
+        elif grid * 2 <= maxwg and (ragged or nk >= 8 * KV_TILE):
             gs = 2
-        if grid * gs > maxwg or grid * gs > ATTN_PARTIAL_WG:               # :2023-2024
+        if grid * gs > maxwg or grid * gs > ATTN_PARTIAL_WG:               # the two caps
             gs = 1
         if gs > 1:
-            return f"attention_dma_kernel<{dh}, {rd}, 1, {gs}, 0, 0>"     # :2030-2046
-    if dh == 64 and grid <= 256 and (ragged or nk >= 4 * KV_TILE):         # :2049 key split
+            return f"attention_dma_kernel<{dh}, {rd}, 1, {gs}, 0, 0>"     # AttnFamily::GSPLIT2 / GSPLIT4
+    if dh == 64 and grid <= 256 and (ragged or nk >= 4 * KV_TILE):         # key split (AttnFamily::KSPLIT)
         return f"attention_dma_kernel<64, {rd}, 2, 1, 0, 0>"
-    if dh in (16, 128):                                                    # :2100-2128
+    if dh in (16, 128):                                                    # AttnFamily::REG
         return f"attention_kernel<{dh}, {rd}>"
     return f"attention_dma_kernel<{dh}, {rd}, 1, 1, 0, 0>"
 

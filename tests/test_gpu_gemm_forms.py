@@ -63,9 +63,9 @@ def _cdiv(a, b):
 
 # ----------------------------------------------------------------------------- 0. the selection rules, restated
 def expected_f32(M, N, K, batch=1, a_kmajor=False, b_kmajor=False):
-    """The instance og_launch_gemm (gemm_f32.hip:301-334) launches in the default environment.  The 128 x 128 tile needs
+    """The instance og_launch_gemm (gemm_f32.hip) launches in the default environment.  The 128 x 128 tile needs
     OG_GEMM_F32_BN=128 (experiment-only): out of scope here.  No caller passes a ragged descriptor: RaggedNone always."""
-    bm = 128 if _cdiv(M, 128) * batch * _cdiv(N, 64) >= 1024 else 64          # :303-307
+    bm = 128 if _cdiv(M, 128) * batch * _cdiv(N, 64) >= 1024 else 64          # narrow / shortt there
     tf = lambda b: "true" if b else "false"
     return f"gemm_nt_f32_kernel<{bm}, 64, {tf(a_kmajor)}, {tf(b_kmajor)}, RaggedNone>"
 
@@ -75,36 +75,36 @@ EM_RUNTIME, EM_NONE, EM_RELU, EM_RES_HL = 0, 1, 2, 3          # gemm_f16x3.hip:2
 
 def expected_f16x3(M, N, K, batch=1, c32=False, planes=False, hl=False, relu=False, res32=False, res_hl=False, alpha=False, ct=False,
                    ragged=False):
-    """The instance og_launch_gemm_f16x3 (gemm_f16x3.hip:1217-1277) launches in the default environment.  planes / hl: the split-f16
+    """The instance og_launch_gemm_f16x3 (gemm_f16x3.hip) launches in the default environment.  planes / hl: the split-f16
     output as two planes (Ch, Cl) or as hl32 rows; M, N of a ragged launch: the largest pair's."""
     nz = batch if batch > 1 else 1
     rd = "RaggedDesc" if ragged else "RaggedNone"
     ch = planes or hl
-    fits = (N % 256 == 0 or nz > 1) and _cdiv(M, 256) * _cdiv(N, 256) * nz >= 192 and not alpha and not ct          # :1221
+    fits = (N % 256 == 0 or nz > 1) and _cdiv(M, 256) * _cdiv(N, 256) * nz >= 192 and not alpha and not ct          # gemm_big_tile_allowed
     if fits:
-        if nz == 1 and not ragged:                                                                                   # :1225
-            whole = M % 256 == 0 and N % 256 == 0 and ch and not c32                                                 # :1226
+        if nz == 1 and not ragged:                                                                                   # gemm_big2_allowed
+            whole = M % 256 == 0 and N % 256 == 0 and ch and not c32
             em = EM_RUNTIME
-            if not res32 and not res_hl:                                                                             # :1232-1236
+            if not res32 and not res_hl:
                 em = EM_RELU if relu else EM_NONE
             elif not relu and res_hl:
                 em = EM_RES_HL
-            if whole and hl:                                                                                         # :1238-1242
+            if whole and hl:
                 return f"gemm_nt_f16x3_big2_kernel<1, {em}>"
-            if whole and planes:                                                                                     # :1243-1245
+            if whole and planes:
                 return f"gemm_nt_f16x3_big2_kernel<2, {em if em == EM_NONE else EM_RUNTIME}>"
-            return "gemm_nt_f16x3_big2_kernel<0, 0>"                                                                 # :1246
-        return f"gemm_nt_f16x3_big_kernel<{rd}>"                                                                     # :1250
-    if N > 64:                                                                                                       # :1256
+            return "gemm_nt_f16x3_big2_kernel<0, 0>"
+        return f"gemm_nt_f16x3_big_kernel<{rd}>"
+    if N > 64:
         if not ragged:
-            whole = nz == 1 and M % 128 == 0 and N % 128 == 0 and ch and not c32 and not ct and not alpha and not res32       # :1260
+            whole = nz == 1 and M % 128 == 0 and N % 128 == 0 and ch and not c32 and not ct and not alpha and not res32
             if whole:
-                if hl and not res_hl and relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 1, 2>"              # :1264
-                if hl and not res_hl and not relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 1, 1>"          # :1265
-                if hl and res_hl and not relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 1, 3>"              # :1266
-                if planes and not res_hl and not relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 2, 1>"      # :1267
-        return f"gemm_nt_f16x3_kernel<128, 2, {rd}, 0, 0>"                                                           # :1271
-    return f"gemm_nt_f16x3_kernel<64, 2, {rd}, 0, 0>"                                                                # :1273
+                if hl and not res_hl and relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 1, 2>"
+                if hl and not res_hl and not relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 1, 1>"
+                if hl and res_hl and not relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 1, 3>"
+                if planes and not res_hl and not relu: return "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 2, 1>"
+        return f"gemm_nt_f16x3_kernel<128, 2, {rd}, 0, 0>"
+    return f"gemm_nt_f16x3_kernel<64, 2, {rd}, 0, 0>"
 
 
 def test_restatement_sides_of_the_boundaries():
@@ -686,7 +686,7 @@ def _scores64(ctx0, ctx1, sd, cfg):
 @pytest.mark.parametrize("residual", [True, False])
 @pytest.mark.parametrize("B,m,n", [(1, 130, 97), (3, 130, 97), (3, 300, 257)])
 def test_forward_final_projection(gpu_device, B, m, n, residual):
-    """The final projection (api.hip:698-708): alpha + Ct with residual=True, Ct alone without.  x: the residual stream at the last tap
+    """The final projection (api.hip: forward_impl): alpha + Ct with residual=True, Ct alone without.  x: the residual stream at the last tap
     (the (hi, lo) rows the launch reads, merged); the returned context descriptors are channel-first, so this checks the transposed store.
     Then the score launch of the same call (one pair: batch = 0; three pairs: a batched launch on the 128 tile) from those descriptors."""
     cfg, sd, model = _model(residual=residual)
@@ -795,7 +795,7 @@ def test_forward_scores_big_batch_ragged(gpu_device):
 
 @gpu
 def test_forward_cross_layer_row_split(gpu_device):
-    """The row-split launch of a cross layer (api.hip:663-674): k | v | q of image 1 and the q of image 0 in ONE 256-tile launch whose rows
+    """The row-split launch of a cross layer (api.hip: forward_impl): k | v | q of image 1 and the q of image 0 in ONE 256-tile launch whose rows
     below T0 stop after the q columns.  It needs T0 and T multiples of 256, more than 8192 rows (below, proj_small takes the launch; the
     stream kernel only at D = 128) and at least 192 blocks: B = 2, m = 128, n = 8192 gives T0 = 256, T = 16640, 1 + 64 x 3 = 193 blocks.
     The launch is big2<2, 1> like the self layer's; that it was ONE launch shows in the kernel list: two 256-tile launches per stage and a

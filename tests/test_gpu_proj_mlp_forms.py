@@ -77,28 +77,28 @@ def _cdiv(a, b):
 
 # ----------------------------------------------------------------------------- 0. the selection rules, restated
 def expected_mlp(M, D, b0_aligned=True, b3_aligned=True):
-    """og_launch_mlp_fused (mlp_fused.hip:1410-1425): 32-token workgroups up to 8192 rows (og_mlp_small_wanted, :1404-1408) when both
-    biases can be read as 16-byte vectors (:1416), the 128-token tile kernel otherwise."""
+    """og_launch_mlp_fused (mlp_fused.hip): 32-token workgroups up to 8192 rows (og_mlp_small_wanted) when both
+    biases can be read as 16-byte vectors, the 128-token tile kernel otherwise."""
     small = M <= 8192 and b0_aligned and b3_aligned
     return f"mlp_small_kernel<{D}>" if small else f"mlp_fused_kernel<{D}>"
 
 
 def expected_proj_block(M, K, N, a, b, ldy, split_row=0, planes_aligned=True):
-    """og_proj_block (mlp_fused.hip:1577-1590).  a, b: block ranges (units of 32 channels) of the rows below / from split_row."""
-    stream = (M > 8192 and N % 128 == 0                                                        # :1585: more than 8192 rows, a batch stream exists
+    """og_proj_block (mlp_fused.hip).  a, b: block ranges (units of 32 channels) of the rows below / from split_row."""
+    stream = (M > 8192 and N % 128 == 0                                                        # more than 8192 rows, a batch stream exists
               and all(v % 4 == 0 for v in (*a, *b)) and a[1] - a[0] <= 32 and b[1] - b[0] <= 32     # whole 128-channel groups, at most 8 of them
-              and ldy % 64 == 0 and not (0 < split_row < M and split_row % 128)                # :1586: plane rows of whole lines, a tile-aligned split
+              and ldy % 64 == 0 and not (0 < split_row < M and split_row % 128)                # plane rows of whole lines, a tile-aligned split
               and planes_aligned)                                                              # 128-byte aligned planes
     return f"proj_stream_kernel<{K}>" if stream else f"proj_small_kernel<{K}>"
 
 
 def proj_small_grid(M, a, b):
-    """og_launch_proj_small (mlp_fused.hip:1492-1496) -> (parts, bpp, workgroups)."""
+    """og_launch_proj_small (mlp_fused.hip) -> (parts, bpp, workgroups)."""
     tiles, nblk = _cdiv(M, 32), max(a[1] - a[0], b[1] - b[0])
     parts, bpp = 1, max(nblk, 1)
-    if nblk > 8 and tiles * _cdiv(nblk, 8) <= 256:         # :1495: few tiles: 8 blocks (one per wave) per workgroup
+    if nblk > 8 and tiles * _cdiv(nblk, 8) <= 256:         # few tiles: 8 blocks (one per wave) per workgroup
         parts, bpp = _cdiv(nblk, 8), 8
-    if nblk > 24:                                          # :1496: a workgroup covers at most 3 blocks per wave
+    if nblk > 24:                                          # a workgroup covers at most 3 blocks per wave
         parts, bpp = _cdiv(nblk, 8), 8
     return parts, bpp, tiles * parts
 
@@ -123,38 +123,38 @@ def proj_small_forms(M, a, b, split_row=0):
 
 
 def expected_forward(D, B, m, n, stages=1):
-    """og_forward's routing of the q | k | v projections and the message MLP (api.hip:592-686) for softmax attention: the multiset of the
+    """og_forward's routing of the q | k | v projections and the message MLP (api.hip: forward_impl) for softmax attention: the multiset of the
     four kernels of mlp_fused.hip over `stages` self + cross layers.  Launches that go to the tile GEMMs are not counted here
     (tests/test_gpu_gemm_forms.py pins those)."""
     T0, T1, QW = B * m, B * n, 3 * D
     T = T0 + T1
     ps, pst = f"proj_small_kernel<{D}>", f"proj_stream_kernel<{D}>"
     c = Counter()
-    small_ok = lambda R: R <= 8192                                         # :592-595 (a fragment-major copy exists at D = 256 / 128)
-    stream_ok = lambda R: R > 8192 and D == 128                            # :605-608 + og_proj_stream_wanted (mlp_fused.hip:1538-1543)
+    small_ok = lambda R: R <= 8192                                         # og_proj_small_wanted (a fragment-major copy exists at D = 256 / 128)
+    stream_ok = lambda R: R > 8192 and D == 128                            # og_proj_stream_wanted
 
-    def qkv(r0, R, c0, c1):                                                # :614-627
+    def qkv(r0, R, c0, c1):
         if small_ok(R) and c0 % 32 == 0 and c1 % 32 == 0:
             c[ps] += 1
         elif stream_ok(R) and c0 % 128 == 0 and c1 % 128 == 0 and (r0 * QW * 2) % 128 == 0:
             c[pst] += 1
 
-    def mlp(R):                                                            # :632-639: the packed biases start 256-byte aligned sections
+    def mlp(R):                                                            # the packed biases start 256-byte aligned sections
         c[expected_mlp(R, D)] += 1
 
     for _ in range(stages):
-        qkv(0, T, 0, QW); mlp(T)                                           # :649-651 self layer: both images in one launch each
-        if small_ok(T) and T0 % 32 == 0:                                   # :668 one proj_small launch with a row split
+        qkv(0, T, 0, QW); mlp(T)                                           # self layer: both images in one launch each
+        if small_ok(T) and T0 % 32 == 0:                                   # one proj_small launch with a row split
             c[ps] += 1
-        elif stream_ok(T) and T0 % 128 == 0 and D % 128 == 0:              # :670 one proj_stream launch with a row split
+        elif stream_ok(T) and T0 % 128 == 0 and D % 128 == 0:              # one proj_stream launch with a row split
             c[pst] += 1
         elif D % 256 == 0 and T0 % 256 == 0 and T % 256 == 0 and T0 // 256 + (T1 // 256) * (QW // 256) >= 192:
-            pass                                                           # :672 the 256-tile GEMM with a row split (gemm_f16x3.hip:1179-1187)
-        else:                                                              # :676-677
+            pass                                                           # the 256-tile GEMM with a row split (og_gemm_f16x3_row_split_ok)
+        else:
             qkv(T0, T1, 0, QW); qkv(0, T0, 0, D)
-        mlp(T0)                                                            # :686 side 0
-        qkv(0, T0, D, QW)                                                  # :681 k | v of the updated image 0
-        mlp(T1)                                                            # :686 side 1
+        mlp(T0)                                                            # side 0
+        qkv(0, T0, D, QW)                                                  # k | v of the updated image 0
+        mlp(T1)                                                            # side 1
     return c
 
 
@@ -339,7 +339,7 @@ def test_mlp_fused_by_size(gpu_device, D, M):
 @pytest.mark.parametrize("M", [1, 127, 128, 129, 200])
 @pytest.mark.parametrize("D", [256, 128])
 def test_mlp_unaligned_bias_takes_the_tile_kernel(gpu_device, D, M):
-    """A bias that cannot be read as 16-byte vectors sends a launch of few rows to mlp_fused_kernel (mlp_fused.hip:1416): one tile holding
+    """A bias that cannot be read as 16-byte vectors sends a launch of few rows to mlp_fused_kernel (og_launch_mlp_fused): one tile holding
     1 / 127 / 128 rows, two tiles.  The same operands with aligned biases run mlp_small_kernel; the two agree within the bound the existing
     test uses between the fused and the two-launch form."""
     d = _mlp_data(M, D)
@@ -451,7 +451,7 @@ def test_proj_small_full(gpu_device, K, M):
 @gpu
 @pytest.mark.parametrize("K,M,parts", [(256, 2720, 3), (256, 2721, 1), (128, 4096, 2), (128, 4097, 1)])
 def test_proj_small_deal_out_threshold(gpu_device, K, M, parts):
-    """Both sides of tiles * parts <= 256 (mlp_fused.hip:1495) on the whole q | k | v matrix: 85 x 3 / 86 x 3 at 24 blocks, 128 x 2 / 129 x 2 at
+    """Both sides of tiles * parts <= 256 (og_launch_proj_small) on the whole q | k | v matrix: 85 x 3 / 86 x 3 at 24 blocks, 128 x 2 / 129 x 2 at
     12.  Not dealt out, a wave owns 3 blocks (K = 256) or 2 / 1 (K = 128)."""
     N = 3 * K
     assert proj_small_grid(M, *_full(N))[0] == parts
