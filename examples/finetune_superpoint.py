@@ -11,7 +11,10 @@ in train(), its parameters keep requires_grad, and the matcher's loss is back-pr
 Weights are seeded (no checkpoint is needed); the frames are synthetic, as in examples/pretrain_homography.py.  By default every step
 draws the SAME pair, so that the printed loss is one curve; --fresh draws a new pair per step, as a data loader would.
 
-    python examples/finetune_superpoint.py [--steps 6] [--pairs 2] [--size 240 320] [--offset 24] [--keypoints 256] [--fresh]"""
+--bn fine-tunes SuperPointNetBn instead (the reference's superpoint_coco / superpoint_kitti configurations): every BatchNorm2d runs on
+batch statistics and moves its running buffers (csrc/superpoint_bn_train.hip), and its weight and bias are optimised with the rest.
+
+    python examples/finetune_superpoint.py [--steps 6] [--pairs 2] [--size 240 320] [--offset 24] [--keypoints 256] [--fresh] [--bn]"""
 import argparse
 import os
 import sys
@@ -24,16 +27,16 @@ from examples.train_fit import GAMMA, MAX_GRAD_NORM                    # noqa: E
 from examples.train_step import MARGIN, training_step                  # noqa: E402
 from openglue_amd import optim, pairs, synthetic as syn                # noqa: E402
 from openglue_amd.superglue import SuperGlue                           # noqa: E402
-from openglue_amd.superpoint import SuperPointNet                      # noqa: E402
+from openglue_amd.superpoint import SuperPointNet, SuperPointNetBn     # noqa: E402
 
 
-def run(steps=6, n_pairs=2, size=(240, 320), offset=24, keypoints=256, stages=3, lr=1e-4, fresh=False, seed=0, log=print):
+def run(steps=6, n_pairs=2, size=(240, 320), offset=24, keypoints=256, stages=3, lr=1e-4, fresh=False, seed=0, log=print, bn=False):
     """-> [(matched labels, total loss, |grad| of conv1a.weight)] per step"""
     dev = torch.device("cuda:0")
     H, W = size
     frames = make_frames(n_pairs, H, W, dev, seed)
-    extractor = SuperPointNet(max_keypoints=keypoints, keypoint_threshold=0.005)
-    extractor.load_state_dict(syn.make_superpoint_state_dict(False, seed=1))
+    extractor = (SuperPointNetBn if bn else SuperPointNet)(max_keypoints=keypoints, keypoint_threshold=0.005)
+    extractor.load_state_dict(syn.make_superpoint_state_dict(bn, seed=1))
     extractor = extractor.to(dev).train()                                  # finetune: True
     cfg = syn.make_config(descriptor_dim=256, num_stages=stages, num_heads=4, num_iters=20, side_info_size=1)
     model = SuperGlue(cfg)
@@ -72,5 +75,6 @@ if __name__ == "__main__":
     ap.add_argument("--keypoints", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--fresh", action="store_true")
+    ap.add_argument("--bn", action="store_true", help="fine-tune SuperPointNetBn (train-mode BatchNorm)")
     a = ap.parse_args()
-    run(a.steps, a.pairs, tuple(a.size), a.offset, a.keypoints, lr=a.lr, fresh=a.fresh)
+    run(a.steps, a.pairs, tuple(a.size), a.offset, a.keypoints, lr=a.lr, fresh=a.fresh, bn=a.bn)

@@ -652,6 +652,35 @@ int og_superpoint_describe_backward(int32_t batch, int32_t Hc, int32_t Wc, int32
                                     const float* coarse_desc, const float* d_descriptors, float* d_coarse, void* workspace_dev,
                                     void* stream);
 
+/* Fine-tuning SuperPointNetBn: train-mode BatchNorm2d behind every convolution (csrc/superpoint_bn_train.hip; reference
+ * models/features/superpoint/model.py:180-199 with the modules in train()).  Exact fp32, no atomics, every sum in a fixed order.
+ * Additive to ABI v14.  B * (H / 8) * (W / 8) >= 2: one value per channel has no batch variance (the byte queries return 0).
+ *
+ * og_superpoint_bn_train_forward: packed_dev = the blob of og_superpoint_pack(..., batch_norm = 0, ...): the RAW weights.  bn (host
+ *   array of 40 device pointers): weight, bias, running_mean, running_var of bn1a, bn1b, bn2a, ..., bn4b, bnPa, bnDa in this order;
+ *   eps, momentum (host, 10 floats): per module.  Every layer's batch statistics are taken over the B h w pixels it convolves at, the
+ *   running buffers are updated in place (running_var with the unbiased variance), like torch.  `saved`
+ *   (og_superpoint_bn_train_saved_bytes, 16-byte aligned) begins with the hidden map of the two heads, [B Hc Wc][512]:
+ *   relu(bnPa(convPa)) | relu(bnDa(convDa)).  convPb / bnPb / convDb / bnDb are the caller's (og_gemm_nt, og_batchnorm_train_*), then:
+ * og_superpoint_bn_cell_tail: logits [B Hc Wc][ld_logits] (65 used, after bnPb) -> softmax, dustbin dropped, depth-to-space ->
+ *   heatmap [B][Hc*8][Wc*8]; desc_raw [B Hc Wc][256] (after bnDb) -> coarse_desc, unit L2 norm per cell.
+ * og_superpoint_bn_train_backward: g_hidden = the gradient of the hidden map AFTER its ReLU (the mask is applied here, from the saved
+ *   raw output).  packed_grad_dev, first_layer, grads and workspace alignment as og_superpoint_train_backward; the bias slots of `grads`
+ *   are not written (the mean subtraction removes the convolution biases: their gradient is zero).  bn_grads [2][1280]: d weight then
+ *   d bias of the BatchNorm layers, channels in the order bn1a (64), bn1b, bn2a, bn2b (64 each), bn3a, bn3b, bn4a, bn4b (128 each),
+ *   bnPa | bnDa (512); written for every layer visited (layer j's BatchNorm with layer j; bn1a when first_layer == 0).
+ *   layer_grads (debug, may be NULL): dz = the gradient of the raw convolution output, dense, [B][H][W][64] of conv1a first and then
+ *   [B][h_j][w_j][Cout_j] for j = 0..7.  One workspace (og_superpoint_bn_train_workspace_bytes, 16-byte aligned) serves both calls. */
+size_t og_superpoint_bn_train_saved_bytes(int32_t batch, int32_t H, int32_t W);
+size_t og_superpoint_bn_train_workspace_bytes(int32_t batch, int32_t H, int32_t W);
+int og_superpoint_bn_train_forward(int32_t batch, int32_t H, int32_t W, const float* image, const void* packed_dev, float* const* bn,
+                                   const float* eps, const float* momentum, void* saved_dev, void* workspace_dev, void* stream);
+int og_superpoint_bn_cell_tail(int32_t batch, int32_t Hc, int32_t Wc, const float* logits, int64_t ld_logits, const float* desc_raw,
+                               float* heatmap, float* coarse_desc, void* stream);
+int og_superpoint_bn_train_backward(int32_t batch, int32_t H, int32_t W, const float* image, const void* packed_grad_dev,
+                                    const void* saved_dev, const float* g_hidden, int32_t first_layer, float* grads, float* bn_grads,
+                                    float* layer_grads, void* workspace_dev, void* stream);
+
 /* ABI v14 -- the reference's optimizer step: torch.optim.Adam + StepLR(step_size=1) stepped every iteration (models/matching_module.py:133-147)
  * behind torch.nn.utils.clip_grad_norm_ (train.py:73 gradient_clip_val), fused into three launches whatever the number of parameters
  * (csrc/optimizer.hip).  The caller owns three flat fp32 device buffers grad / exp_avg / exp_avg_sq of layout.total floats in which

@@ -193,6 +193,11 @@ SYMBOLS = {
     "og_superpoint_train_forward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_superpoint_train_backward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp]),
     "og_superpoint_describe_backward": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "og_superpoint_bn_train_saved_bytes": (_sz, [_i32, _i32, _i32]),
+    "og_superpoint_bn_train_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "og_superpoint_bn_train_forward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_superpoint_bn_cell_tail": (C.c_int, [_i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "og_superpoint_bn_train_backward": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
     "og_sift_geometry":(C.c_int, [_i32, _i32, C.POINTER(C.c_int32)]),
     "og_sift_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "og_sift_pyramid": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -1,5 +1,5 @@
 """Which device kernels a piece of host code launched: the names the dispatch tests (tests/test_gpu_attention_dispatch.py, tests/test_gpu_gemm_forms.py, tests/test_gpu_proj_mlp_forms.py,
-tests/test_gpu_attention_backward.py, tests/test_gpu_sinkhorn_forms.py, tests/test_gpu_superpoint_train_forms.py) and the form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
+tests/test_gpu_attention_backward.py, tests/test_gpu_sinkhorn_forms.py, tests/test_gpu_superpoint_train_forms.py, tests/test_gpu_superpoint_bn_train_forms.py) and the form checks (scripts/check_attention_pipe.py) assert on.  It lives in the package, not under tests/, so that the scripts can use it on
 their own.
 
 launched_kernels(fn) runs fn() under torch.profiler (ProfilerActivity.CUDA: on ROCm, kineto's roctracer records every dispatched kernel
@@ -20,7 +20,10 @@ SINKHORN = ("sinkhorn_sweep_kernel<", "sinkhorn_sweep_fast_kernel<", "sinkhorn_c
             "sinkhorn_resident_kernel<", "sinkhorn_fallback_kernel<")     # csrc/sinkhorn.hip, csrc/sinkhorn_resident.hip: the inference Sinkhorn
 SUPERPOINT_TRAIN = ("sp_conv3x3_save_kernel<", "sp_dgrad_kernel<", "sp_wgrad_kernel<", "sp_wgrad1a_kernel", "sp_reduce_parts_kernel", "sp_describe_bwd_point_kernel",
                     "sp_describe_bwd_cell_kernel", "sp_grad_dump_kernel<")     # csrc/superpoint_train.hip: the SuperPoint fine-tuning kernels
-PROJ_WSTAT = "proj_wstat_kernel"       # csrc/proj_wstat.hip: the weight-stationary q | k | v projection of 256-d batches (no template arguments)
+SUPERPOINT_BN_TRAIN = ("sp_bn_conv1a_kernel", "sp_bn_conv3x3_kernel<", "sp_bn_stats_finish_kernel", "sp_bn_act_kernel", "sp_bn_cell_tail_kernel", "sp_bn_reduce_kernel<",
+                       "sp_bn_reduce_finish_kernel", "sp_bn_dgrad_kernel<", "sp_bn_wgrad_kernel<", "sp_bn_wgrad1a_kernel", "sp_bn_dz_dump_kernel<",
+                       "sp_reduce_parts_kernel")     # csrc/superpoint_bn_train.hip: the SuperPointNetBn fine-tuning kernels
+PROJ_WSTAT ="proj_wstat_kernel"       # csrc/proj_wstat.hip: the weight-stationary q | k | v projection of 256-d batches (no template arguments)
 
 
 def short_name(name: str) -> str:
@@ -91,3 +94,8 @@ def sinkhorn_instances(names) -> list:
 def superpoint_train_instances(names) -> list:
     """The SuperPoint fine-tuning launches (csrc/superpoint_train.hip) among `names`, in launch order, one entry per launch."""
     return [n for n in names if n.startswith(SUPERPOINT_TRAIN)]
+
+
+def superpoint_bn_train_instances(names) -> list:
+    """The SuperPointNetBn fine-tuning launches (csrc/superpoint_bn_train.hip) among `names`, in launch order, one entry per launch."""
+    return [n for n in names if n.startswith(SUPERPOINT_BN_TRAIN)]

@@ -1,5 +1,5 @@
 """SuperPoint detector and descriptor on HIP kernels: drop-ins for SuperPointNet / SuperPointNetBn of the reference
-(models/features/superpoint/model.py).  Inference for both; SuperPointNet is also differentiable (the reference's `finetune: True`).
+(models/features/superpoint/model.py).  Inference and fine-tuning (the reference's `finetune: True`) for both.
 
 Same constructor arguments and defaults, same state-dict keys and shapes, same `weights=` loading, and `forward(image, mask=None)`
 returns (lafs [B, N, 2, 3], scores [B, N], descriptors [B, N, 256]) -- what features.prepare_features_output and
@@ -17,6 +17,10 @@ Fine-tuning: SuperPointNet.forward in train() mode, with grad enabled and a para
 with a grad_fn (_SuperPointTrain: csrc/superpoint_train.hip for the ten 3x3 layers and the descriptor sampling, the exact-fp32 GEMM of
 train.py for the two 1x1 heads, tensor algebra for the softmax / L2-norm derivatives at coarse resolution).  Same values as eval(), bit
 for bit; the selection stays the inference kernels and carries no gradient, as in the reference.
+
+SuperPointNetBn in train() mode (_SuperPointBnTrain, csrc/superpoint_bn_train.hip): every BatchNorm2d normalises with the statistics of
+its own batch and moves its running buffers, with grad enabled or not, like nn.BatchNorm2d; scores and descriptors carry a grad_fn
+for the 24 convolution and 24 BatchNorm parameters.  The selection runs on the batch-statistics heatmap.  eval() is the folded blob.
 """
 from __future__ import annotations
 
@@ -65,6 +69,8 @@ class SuperPointNet(nn.Module):
         self._packed_key = None
         self._packed_grad: Optional[torch.Tensor] = None
         self._packed_grad_key = None
+        self._packed_raw: Optional[torch.Tensor] = None
+        self._packed_raw_key = None
         self.keep_layer_grads = False                # debug: backward leaves the per-layer pre-activation gradients in self.layer_grads
         self.layer_grads = {}
         self._load_weights(weights)
@@ -105,8 +111,8 @@ class SuperPointNet(nn.Module):
 
     # ---------------------------------------------------------------- checks
     def _check(self, image: torch.Tensor):
-        if self._batch_norm and self.training:
-            raise NotImplementedError(f"{type(self).__name__}: training-mode BatchNorm is not supported; call .eval()")
+        if self._batch_norm and self.training and isinstance(image, torch.Tensor) and not image.is_cuda:
+            raise NotImplementedError(f"{type(self).__name__}: no CPU path for training-mode BatchNorm; move the image to the GPU or call .eval()")
         if self.descriptor_dim != 256:
             raise ValueError(f"descriptor_dim must be 256, got {self.descriptor_dim}")
         k = int(self.nms_kernel)
@@ -122,6 +128,14 @@ class SuperPointNet(nn.Module):
             raise ValueError(f"image {list(image.shape)}: H // 8 and W // 8 must be >= 1")
         if not image.is_cuda:
             raise RuntimeError("SuperPoint: expected an image tensor on the GPU; openglue_amd has no CPU path")
+        if self._batch_norm and self.training:
+            if image.shape[0] * (image.shape[2] // 8) * (image.shape[3] // 8) < 2:
+                raise ValueError(f"image {list(image.shape)}: training-mode BatchNorm needs more than one value per channel "
+                                 "(B * (H // 8) * (W // 8) >= 2)")
+            for n in BN_NAMES:
+                m = getattr(self, n)
+                if m.momentum is None or not m.track_running_stats:
+                    raise ValueError(f"{n}: training-mode BatchNorm needs a momentum and track_running_stats=True")
 
     # ---------------------------------------------------------------- stages
     def dense(self, image: torch.Tensor, workspace: Optional[torch.Tensor] = None):
@@ -172,8 +186,9 @@ class SuperPointNet(nn.Module):
         return self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
 
     def _pack_grad(self, device: torch.device) -> torch.Tensor:
-        """The data-gradient blob (weights transposed, taps flipped), repacked when a weight changes -- as _pack."""
-        ts = self._pack_tensors()
+        """The data-gradient blob (weights transposed, taps flipped), repacked when a weight changes -- as _pack.  It holds the 24
+        convolution tensors only: a BatchNorm buffer that moves (every train-mode step of SuperPointNetBn) does not rebuild it."""
+        ts = self._pack_tensors()[:2 * len(CONV_NAMES)]
         key = (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
         if self._packed_grad is not None and self._packed_grad_key == key:
             return self._packed_grad
@@ -186,13 +201,30 @@ class SuperPointNet(nn.Module):
         self._packed_grad_key = key
         return self._packed_grad
 
+    def _pack_raw(self, device: torch.device) -> torch.Tensor:
+        """The forward blob of the convolutions alone (no BatchNorm folded in): what the train-mode BatchNorm path convolves with."""
+        ts = [t for n in CONV_NAMES for t in (getattr(self, n).weight, getattr(self, n).bias)]
+        key = (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
+        if self._packed_raw is not None and self._packed_raw_key == key:
+            return self._packed_raw
+        lib = _lib.load()
+        host = [t.detach().to("cpu", torch.float32).contiguous() for t in ts]
+        ptrs = (C.c_void_p * len(host))(*[h.data_ptr() for h in host])
+        blob = torch.empty(lib.og_superpoint_packed_bytes(self.descriptor_dim), dtype=torch.uint8)
+        _lib.check(lib.og_superpoint_pack(self.descriptor_dim, 0, 0.0, ptrs, blob.data_ptr()), "og_superpoint_pack")
+        self._packed_raw = blob.to(device)
+        self._packed_raw_key = key
+        return self._packed_raw
+
     def forward(self, image: torch.Tensor, mask=None):
         """image [B, 1, H, W] -> lafs [B, N, 2, 3], scores [B, N], descriptors [B, N, 256] (mask is ignored, as in the reference).
         In train() mode with grad enabled and a parameter that requires grad, scores and descriptors carry a grad_fn."""
         self._check(image)
+        if self._batch_norm and self.training:       # batch statistics, running buffers updated: also under torch.no_grad()
+            convs = [t for n in CONV_NAMES for t in (getattr(self, n).weight, getattr(self, n).bias)]
+            bns = [t for n in BN_NAMES for t in (getattr(self, n).weight, getattr(self, n).bias)]
+            return _SuperPointBnTrain.apply(self, image, *convs, *bns)
         if self._differentiable():
-            if self._batch_norm:
-                raise NotImplementedError(f"{type(self).__name__}: the backward is implemented for SuperPointNet only")
             return _SuperPointTrain.apply(self, image, *self._pack_tensors())
         with torch.no_grad():
             B, _, H, W = image.shape
@@ -218,6 +250,21 @@ def _grad_slices():
 
 _GRAD_SLICES, _GRAD_FLOATS = _grad_slices()
 _TRUNK = CONV_NAMES[:8]                              # first_layer of og_superpoint_train_backward: index into this list, 8 = heads only
+
+
+def _softmax65_backward(logit: torch.Tensor, dp: torch.Tensor) -> torch.Tensor:
+    """float64 logits [npix, 65] and the gradient dp [npix, 64] of the 64 kept probabilities -> the gradient of the logits, in the
+    cancellation-free form _SuperPointTrain.backward describes."""
+    npix = logit.shape[0]
+    e = torch.exp(logit - logit.max(dim=1, keepdim=True).values)
+    zero = torch.zeros(npix, 1, device=logit.device, dtype=torch.float64)
+    before = torch.cat([zero, torch.cumsum(e, 1)[:, :-1]], 1)
+    after = torch.cat([torch.cumsum(e.flip(1), 1)[:, :-1].flip(1), zero], 1)
+    Z = before[:, -1:] + e[:, -1:]
+    prob, rest = e / Z, (before + after) / Z
+    dp65 = torch.cat([dp, zero], 1)                                                 # the dustbin channel receives no gradient
+    pd = prob * dp65
+    return prob * (dp65 * rest - (pd.sum(1, keepdim=True) - pd))
 
 
 class _SuperPointTrain(torch.autograd.Function):
@@ -296,17 +343,8 @@ class _SuperPointTrain(torch.autograd.Function):
             # up to dlog, in float64 tensor algebra at coarse resolution.
             part = ops.gemm_nt(hP.view(npix, 16, 16).permute(1, 0, 2).contiguous(), Wp.view(68, 16, 16).permute(1, 0, 2).contiguous())
             logit = part.double().sum(0)[:, :65] + bp[:65].double()
-            dp = dp.double()
-            e = torch.exp(logit - logit.max(dim=1, keepdim=True).values)
-            zero = torch.zeros(npix, 1, device=dev, dtype=torch.float64)
-            before = torch.cat([zero, torch.cumsum(e, 1)[:, :-1]], 1)
-            after = torch.cat([torch.cumsum(e.flip(1), 1)[:, :-1].flip(1), zero], 1)
-            Z = before[:, -1:] + e[:, -1:]
-            prob, rest = e / Z, (before + after) / Z
-            dp65 = torch.cat([dp, zero], 1)                                         # the dustbin channel receives no gradient
-            pd = prob * dp65
             dlog = torch.zeros(npix, 68, device=dev, dtype=torch.float32)
-            dlog[:, :65] = prob * (dp65 * rest - (pd.sum(1, keepdim=True) - pd))
+            dlog[:, :65] = _softmax65_backward(logit, dp.double())
             dh, dW, db = train._conv_backward(hP, Wp, dlog, need_hidden, any(need["convPb"]))
             if any(need["convPb"]):
                 grads["convPb"] = [dW[:65].reshape(65, 256, 1, 1).contiguous(), db[:65].contiguous()]
@@ -353,8 +391,179 @@ class _SuperPointTrain(torch.autograd.Function):
         return result()
 
 
+_BN_TRUNK = BN_NAMES[:8] + ["bnPa", "bnDa"]         # the modules og_superpoint_bn_train_forward normalises with, in its order
+_BN_OFFSETS = dict(zip(_BN_TRUNK, [0, 64, 128, 192, 256, 384, 512, 640, 768, 1024]))      # their channels in bn_grads [2][1280]
+
+
+class _SuperPointBnTrain(torch.autograd.Function):
+    """SuperPointNetBn.forward in train() mode: batch statistics in every BatchNorm, running buffers updated, with a backward.
+    Inputs: the module, the image, weight and bias of CONV_NAMES in order, then weight and bias of BN_NAMES in order.
+    csrc/superpoint_bn_train.hip runs the ten 3x3 layers with their BatchNorms; convPb / convDb are the exact-fp32 GEMM, bnPb / bnDb
+    og_batchnorm_train_forward on the [B Hc Wc] token rows (65 channels padded to 68)."""
+
+    @staticmethod
+    def forward(ctx, net, image, *params):
+        from . import ops, train
+        B, _, H, W = image.shape
+        dev = image.device
+        img = image.detach().to(torch.float32).contiguous()
+        lib = _lib.load()
+        nsaved = lib.og_superpoint_bn_train_saved_bytes(B, H, W)
+        if nsaved == 0:
+            raise ValueError(f"SuperPoint: unsupported image batch [{B}, 1, {H}, {W}] (B * H * W <= 2^26)")
+        mods = [getattr(net, n) for n in _BN_TRUNK]
+        tensors = [t for m in mods for t in (m.weight, m.bias, m.running_mean, m.running_var)]
+        for t in tensors + [net.bnPb.running_mean, net.bnPb.running_var, net.bnDb.running_mean, net.bnDb.running_var]:
+            if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous():
+                raise RuntimeError("SuperPointNetBn: BatchNorm parameters and buffers must be contiguous float32 tensors on the image's device")
+        Hc, Wc = H // 8, W // 8
+        npix = B * Hc * Wc
+        saved = torch.empty(nsaved // 4, device=dev, dtype=torch.float32)
+        wsbuf = _lib.workspace(lib.og_superpoint_bn_train_workspace_bytes(B, H, W), dev)
+        bn = (C.c_void_p * 40)(*[t.data_ptr() for t in tensors])
+        eps = (C.c_float * 10)(*[float(m.eps) for m in mods])
+        mom = (C.c_float * 10)(*[float(m.momentum) for m in mods])
+        _lib.call("og_superpoint_bn_train_forward", dev, B, H, W, img.data_ptr(), net._pack_raw(dev).data_ptr(), bn, eps, mom,
+                  saved.data_ptr(), wsbuf[1], _lib.STREAM)
+        hidden = saved[:npix * 512].view(npix, 512)
+        cP, cD = params[2 * CONV_NAMES.index("convPb"):][:2], params[2 * CONV_NAMES.index("convDb"):][:2]
+        # detector head: convPb, bnPb on 68 channels (the three padding channels are zero and stay out of everything)
+        Wp = torch.zeros(68, 256, device=dev, dtype=torch.float32)
+        Wp[:65] = cP[0].detach().view(65, 256)
+        pad = lambda t, fill: torch.cat([t.detach().to(torch.float32), torch.full((3,), fill, device=dev, dtype=torch.float32)])
+        zP = ops.gemm_nt(hidden[:, :256].contiguous(), Wp, pad(cP[1], 0.0))
+        rm, rv = pad(net.bnPb.running_mean, 0.0), pad(net.bnPb.running_var, 1.0)
+        yP = train.batch_norm_train(zP, pad(net.bnPb.weight, 1.0), pad(net.bnPb.bias, 0.0), rm, rv, float(net.bnPb.momentum), float(net.bnPb.eps))
+        net.bnPb.running_mean.copy_(rm[:65])
+        net.bnPb.running_var.copy_(rv[:65])
+        # descriptor head: convDb, bnDb
+        zD = ops.gemm_nt(hidden[:, 256:].contiguous(), cD[0].detach().view(256, 256).contiguous(), cD[1].detach())
+        yD, meanD, invD = train.batch_norm_train(zD, net.bnDb.weight.detach(), net.bnDb.bias.detach(), net.bnDb.running_mean, net.bnDb.running_var,
+                                                 float(net.bnDb.momentum), float(net.bnDb.eps), return_stats=True)
+        heat = torch.empty(B, Hc * 8, Wc * 8, device=dev, dtype=torch.float32)
+        desc = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
+        _lib.call("og_superpoint_bn_cell_tail", dev, B, Hc, Wc, yP.data_ptr(), 68, yD.data_ptr(), heat.data_ptr(), desc.data_ptr(), _lib.STREAM)
+        for n in BN_NAMES:
+            getattr(net, n).num_batches_tracked += 1
+        # the kernels wrote the running buffers through raw pointers: their _version did not move, so the eval-mode blob (keyed on it)
+        # would be served stale
+        net._packed = net._packed_key = None
+        counts, sidx, sscore, _ = net.detect(heat, net._workspace(B, H, W, dev))
+        n = int(counts[B].item())
+        lafs, scores, descriptors = net.describe(n, sidx, sscore, desc)
+        ctx.net, ctx.n, ctx.shape = net, n, (B, H, W)
+        ctx.save_for_backward(img, saved, desc, sidx, zD, torch.linalg.vector_norm(yD, dim=1, keepdim=True), meanD, invD, *params)
+        ctx.mark_non_differentiable(lafs)
+        return lafs, scores, descriptors
+
+    @staticmethod
+    def backward(ctx, _dlafs, dscores, ddesc):
+        from . import ops, train
+        net, n, (B, H, W) = ctx.net, ctx.n, ctx.shape
+        img, saved, desc, sidx, zD, nrm, meanD, invD, *params = ctx.saved_tensors
+        names = CONV_NAMES + BN_NAMES
+        need = {name: (ctx.needs_input_grad[2 + 2 * i], ctx.needs_input_grad[3 + 2 * i]) for i, name in enumerate(names)}
+        P = {name: (params[2 * i], params[2 * i + 1]) for i, name in enumerate(names)}
+        dev = img.device
+        grads = {name: [None, None] for name in names}
+
+        def result():
+            out = []
+            for name in names:
+                for k in (0, 1):
+                    g = grads[name][k]
+                    if need[name][k] and g is None:  # also every convolution bias: the mean subtraction removes it, its gradient is exactly 0
+                        g = torch.zeros_like(P[name][k])
+                    out.append(g if need[name][k] else None)
+            return (None, None, *out)
+
+        if n == 0:                                   # no keypoint: every gradient is zero, nothing to launch
+            return result()
+        Hc, Wc = H // 8, W // 8
+        npix = B * Hc * Wc
+        hidden = saved[:npix * 512].view(npix, 512)
+        wants = lambda *ns: any(any(need[x]) for x in ns)
+        trunk_first = next((i for i, (c, b) in enumerate(zip(_TRUNK, BN_NAMES[:8])) if wants(c, b)), 8)
+        need_hidden = trunk_first < 8 or wants("convPa", "convDa", "bnPa", "bnDa")
+        g_hidden = torch.zeros(npix, 512, device=dev, dtype=torch.float32)
+
+        # ---- detector head: scores -> softmax over 65 -> bnPb -> convPb, in float64 tensor algebra at coarse resolution from logits
+        # recomputed as 16 exact-fp32 GEMMs over 16 channels each (as _SuperPointTrain.backward, and for its reason)
+        if dscores is not None and (need_hidden or wants("convPb", "bnPb")):
+            dheat = torch.zeros(B, Hc * 8 * Wc * 8, device=dev, dtype=torch.float32)
+            dheat.scatter_(1, sidx[:, :n].long(), dscores.to(torch.float32))
+            dp = dheat.view(B, Hc, 8, Wc, 8).permute(0, 1, 3, 2, 4).reshape(npix, 64)
+            Wp = torch.zeros(68, 256, device=dev, dtype=torch.float32)
+            Wp[:65] = P["convPb"][0].detach().view(65, 256)
+            hP = hidden[:, :256].contiguous()
+            part = ops.gemm_nt(hP.view(npix, 16, 16).permute(1, 0, 2).contiguous(), Wp.view(68, 16, 16).permute(1, 0, 2).contiguous())
+            z = part.double().sum(0)[:, :65] + P["convPb"][1].detach().double()
+            gam, bet = P["bnPb"][0].detach().double(), P["bnPb"][1].detach().double()
+            r = torch.rsqrt(z.var(0, unbiased=False) + float(net.bnPb.eps))
+            xh = (z - z.mean(0)) * r
+            dy = _softmax65_backward(xh * gam + bet, dp.double())
+            dbeta, dgamma = dy.sum(0), (dy * xh).sum(0)
+            dz = torch.zeros(npix, 68, device=dev, dtype=torch.float32)
+            dz[:, :65] = gam * r * (dy - dbeta / npix - xh * (dgamma / npix))
+            dh, dW, _ = train._conv_backward(hP, Wp, dz, need_hidden, need["convPb"][0])
+            grads["bnPb"] = [dgamma.to(torch.float32), dbeta.to(torch.float32)]
+            if need["convPb"][0]:
+                grads["convPb"][0] = dW[:65].reshape(65, 256, 1, 1).contiguous()
+            if need_hidden:
+                g_hidden[:, :256] = dh
+
+        # ---- descriptor head: F.normalize + bilinear sampling (kernels) -> per-cell L2 norm -> bnDb (og_batchnorm_train_backward) -> convDb
+        if ddesc is not None and (need_hidden or wants("convDb", "bnDb")):
+            dd = ddesc.to(torch.float32).contiguous()
+            dcoarse = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
+            wsd = _lib.workspace(B * n * 264 * 4 + 256, dev)
+            _lib.call("og_superpoint_describe_backward", dev, B, Hc, Wc, n, sidx.data_ptr(), sidx.shape[1], desc.data_ptr(), dd.data_ptr(),
+                      dcoarse.data_ptr(), wsd[1], _lib.STREAM)
+            dn, dc = desc.view(npix, 256), dcoarse.view(npix, 256)
+            dy = ((dc - dn * (dn * dc).sum(1, keepdim=True)) / nrm).contiguous()
+            dz = torch.empty_like(dy)
+            dgamma = torch.empty(256, device=dev, dtype=torch.float32)
+            dbeta = torch.empty(256, device=dev, dtype=torch.float32)
+            wsb = train._ws(zD, npix, 256)
+            _lib.call("og_batchnorm_train_backward", dev, zD.data_ptr(), 256, dy.data_ptr(), 256, npix, 256, P["bnDb"][0].detach().data_ptr(),
+                      meanD.data_ptr(), invD.data_ptr(), 0, dz.data_ptr(), 256, dgamma.data_ptr(), dbeta.data_ptr(), wsb.data_ptr(), _lib.STREAM)
+            hD = hidden[:, 256:].contiguous()
+            dh, dW, _ = train._conv_backward(hD, P["convDb"][0].detach().view(256, 256).contiguous(), dz, need_hidden, need["convDb"][0])
+            grads["bnDb"] = [dgamma, dbeta]
+            if need["convDb"][0]:
+                grads["convDb"][0] = dW.reshape(256, 256, 1, 1)
+            if need_hidden:
+                g_hidden[:, 256:] = dh
+
+        # ---- the ten 3x3 layers and their BatchNorms
+        if need_hidden:
+            flat = torch.empty(_GRAD_FLOATS, device=dev, dtype=torch.float32)
+            bnflat = torch.zeros(2, 1280, device=dev, dtype=torch.float32)
+            dbg = None
+            lv = [(H, W, 64), (H, W, 64), (H // 2, W // 2, 64), (H // 2, W // 2, 64), (H // 4, W // 4, 128), (H // 4, W // 4, 128),
+                  (Hc, Wc, 128), (Hc, Wc, 128), (Hc, Wc, 512)]
+            if net.keep_layer_grads:
+                dbg = torch.zeros(sum(B * h * w * c for h, w, c in lv), device=dev, dtype=torch.float32)
+            wsbuf = _lib.workspace(_lib.load().og_superpoint_bn_train_workspace_bytes(B, H, W), dev)
+            _lib.call("og_superpoint_bn_train_backward", dev, B, H, W, img.data_ptr(), net._pack_grad(dev).data_ptr(), saved.data_ptr(),
+                      g_hidden.data_ptr(), trunk_first, flat.data_ptr(), bnflat.data_ptr(), _lib.ptr(dbg), wsbuf[1], _lib.STREAM)
+            for name in _TRUNK[trunk_first:] + ["convPa", "convDa"]:
+                (ow, sw), _ = _GRAD_SLICES[name]
+                grads[name][0] = flat[ow:ow + sw[0] * sw[1] * 9].view(sw)
+            for name in _BN_TRUNK[trunk_first:]:
+                o, c = _BN_OFFSETS[name], getattr(net, name).num_features
+                grads[name] = [bnflat[0, o:o + c], bnflat[1, o:o + c]]
+            if dbg is not None:
+                net.layer_grads, o = {}, 0
+                for name, (h, w, c) in zip(_TRUNK + ["heads"], lv):
+                    net.layer_grads[name] = dbg[o:o + B * h * w * c].view(B, h, w, c)
+                    o += B * h * w * c
+        return result()
+
+
 class SuperPointNetBn(SuperPointNet):
-    """SuperPoint with BatchNorm after every convolution (reference model.py:129); eval mode only."""
+    """SuperPoint with BatchNorm after every convolution (reference model.py:129).  eval(): the BatchNorms folded into the convolutions
+    at pack time.  train(): batch statistics, running buffers updated, differentiable (_SuperPointBnTrain)."""
 
     _batch_norm = True
 
