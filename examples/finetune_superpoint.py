@@ -3,6 +3,7 @@
 in train(), its parameters keep requires_grad, and the matcher's loss is back-propagated through descriptors and responses into it.
 
     uint8 frames --pairs.homography_pairs-->  image0, image1, H
+    --augment weak_color_aug: augment.augment on image0, image1    (what keeps a fine-tuned detector from fitting the training frames)
     SuperPointNet.train() on both views                           -> LAFs, responses (grad_fn), descriptors (grad_fn)
     examples/train_step.py training_step: prepare_features_output -> generate_gt_matches -> SuperGlue.train() -> criterion
     backward (through SuperGlue, side_info / descriptors, csrc/superpoint_train.hip)
@@ -14,7 +15,8 @@ draws the SAME pair, so that the printed loss is one curve; --fresh draws a new 
 --bn fine-tunes SuperPointNetBn instead (the reference's superpoint_coco / superpoint_kitti configurations): every BatchNorm2d runs on
 batch statistics and moves its running buffers (csrc/superpoint_bn_train.hip), and its weight and bias are optimised with the rest.
 
-    python examples/finetune_superpoint.py [--steps 6] [--pairs 2] [--size 240 320] [--offset 24] [--keypoints 256] [--fresh] [--bn]"""
+    python examples/finetune_superpoint.py [--steps 6] [--pairs 2] [--size 240 320] [--offset 24] [--keypoints 256] [--fresh] [--bn]
+                                          [--augment none|weak_color_aug]"""
 import argparse
 import os
 import sys
@@ -25,12 +27,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from examples.pretrain_homography import extract, make_frames          # noqa: E402
 from examples.train_fit import GAMMA, MAX_GRAD_NORM                    # noqa: E402
 from examples.train_step import MARGIN, training_step                  # noqa: E402
-from openglue_amd import optim, pairs, synthetic as syn                # noqa: E402
+from openglue_amd import augment, optim, pairs, synthetic as syn       # noqa: E402
 from openglue_amd.superglue import SuperGlue                           # noqa: E402
 from openglue_amd.superpoint import SuperPointNet, SuperPointNetBn     # noqa: E402
 
 
-def run(steps=6, n_pairs=2, size=(240, 320), offset=24, keypoints=256, stages=3, lr=1e-4, fresh=False, seed=0, log=print, bn=False):
+def run(steps=6, n_pairs=2, size=(240, 320), offset=24, keypoints=256, stages=3, lr=1e-4, fresh=False, seed=0, log=print, bn=False, augmentation="none"):
     """-> [(matched labels, total loss, |grad| of conv1a.weight)] per step"""
     dev = torch.device("cuda:0")
     H, W = size
@@ -44,11 +46,12 @@ def run(steps=6, n_pairs=2, size=(240, 320), offset=24, keypoints=256, stages=3,
     model = model.to(dev).train()
     opt = optim.Adam(list(model.parameters()) + list(extractor.parameters()), lr=lr, max_grad_norm=MAX_GRAD_NORM, scheduler_gamma=GAMMA)
     gen = torch.Generator(device=dev).manual_seed(seed)
+    transform = augment.get_augmentation_transform({"name": augmentation})
     history = []
     for s in range(steps):
         if not fresh:
             gen.manual_seed(seed)
-        item = pairs.homography_pairs(frames, offset, generator=gen)
+        item = augment.augment(pairs.homography_pairs(frames, offset, generator=gen), transform, gen)
         batch = extract(extractor, item)                                    # with grad: scores and descriptors carry a grad_fn
         opt.zero_grad(set_to_none=False)
         out = training_step(model, batch, MARGIN, with_labels=True)
@@ -76,5 +79,6 @@ if __name__ == "__main__":
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--fresh", action="store_true")
     ap.add_argument("--bn", action="store_true", help="fine-tune SuperPointNetBn (train-mode BatchNorm)")
+    ap.add_argument("--augment", default="none", choices=("none", "weak_color_aug"))
     a = ap.parse_args()
-    run(a.steps, a.pairs, tuple(a.size), a.offset, a.keypoints, lr=a.lr, fresh=a.fresh, bn=a.bn)
+    run(a.steps, a.pairs, tuple(a.size), a.offset, a.keypoints, lr=a.lr, fresh=a.fresh, bn=a.bn, augmentation=a.augment)

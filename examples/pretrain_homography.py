@@ -3,6 +3,7 @@
 config/homography_pretraining.yaml, data/oxford_paris_dataset.py) -- from images, on openglue_amd:
 
     uint8 frames --pairs.homography_pairs-->  image0, image1, H      (random corner displacements drawn on the device)
+    --augment weak_color_aug: augment.augment on image0, image1    (equalize, sharpness, solarize, noise; every sample its own draw)
     SIFT (or --features superpoint) on both views                 -> LAFs, responses, descriptors
     examples/train_step.py training_step: prepare_features_output -> generate_gt_matches -> SuperGlue.train() -> criterion
     backward -> openglue_amd.optim.Adam (clip + Adam + StepLR), the constants of examples/train_fit.py
@@ -12,7 +13,8 @@ decoding and resizing.  From there to the parameter update every tensor stays on
 frames and the optimizer step except the extractor's own keypoint count (one integer per image batch) and the numbers printed here.
 A fresh pair is synthesised from the same frames every step, as a data loader would.
 
-    python examples/pretrain_homography.py [--steps 5] [--pairs 2] [--size 240 320] [--offset 24] [--features sift|superpoint]"""
+    python examples/pretrain_homography.py [--steps 5] [--pairs 2] [--size 240 320] [--offset 24] [--features sift|superpoint]
+                                         [--augment none|weak_color_aug]"""
 import argparse
 import os
 import sys
@@ -22,7 +24,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from examples.train_fit import GAMMA, LR, MAX_GRAD_NORM                # noqa: E402
 from examples.train_step import MARGIN, training_step                  # noqa: E402
-from openglue_amd import optim, pairs, synthetic as syn                # noqa: E402
+from openglue_amd import augment, optim, pairs, synthetic as syn       # noqa: E402
 from openglue_amd.sift import SIFT                                     # noqa: E402
 from openglue_amd.superglue import SuperGlue                           # noqa: E402
 from openglue_amd.superpoint import SuperPointNetBn                    # noqa: E402
@@ -53,7 +55,7 @@ def extract(extractor, item):
     return batch
 
 
-def run(steps=5, n_pairs=2, size=(240, 320), offset=24, feature="sift", keypoints=512, stages=3, seed=0, log=print):
+def run(steps=5, n_pairs=2, size=(240, 320), offset=24, feature="sift", keypoints=512, stages=3, seed=0, log=print, augmentation="none"):
     """-> [(matched labels, total loss)] per step"""
     dev = torch.device("cuda:0")
     H, W = size
@@ -65,9 +67,10 @@ def run(steps=5, n_pairs=2, size=(240, 320), offset=24, feature="sift", keypoint
     model = model.to(dev).train()
     opt = optim.Adam(model.parameters(), lr=LR, max_grad_norm=MAX_GRAD_NORM, scheduler_gamma=GAMMA)
     gen = torch.Generator(device=dev).manual_seed(seed)
+    transform = augment.get_augmentation_transform({"name": augmentation})
     history = []
     for s in range(steps):
-        item = pairs.homography_pairs(frames, offset, generator=gen)
+        item = augment.augment(pairs.homography_pairs(frames, offset, generator=gen), transform, gen)
         with torch.no_grad():
             batch = extract(extractor, item)
         opt.zero_grad(set_to_none=False)
@@ -93,5 +96,6 @@ if __name__ == "__main__":
     ap.add_argument("--offset", type=int, default=24)
     ap.add_argument("--features", default="sift", choices=("sift", "superpoint"))
     ap.add_argument("--keypoints", type=int, default=512)
+    ap.add_argument("--augment", default="none", choices=("none", "weak_color_aug"))
     a = ap.parse_args()
-    run(a.steps, a.pairs, tuple(a.size), a.offset, a.features, a.keypoints)
+    run(a.steps, a.pairs, tuple(a.size), a.offset, a.features, a.keypoints, augmentation=a.augment)

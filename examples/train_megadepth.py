@@ -3,6 +3,7 @@
 data/megadepth_dataset.py) -- from frames, on openglue_amd:
 
     uint8 frames, depth maps, K, R, T --megadepth.megadepth_pairs-->  image0, image1, transformation   (random crops drawn on the CPU)
+    --augment weak_color_aug: augment.augment on image0, image1 of the training items (never on the validation item)
     SuperPoint (or --features sift) on both views                  -> LAFs, responses, descriptors
     examples/train_step.py training_step: prepare_features_output -> generate_gt_matches -> SuperGlue.train() -> criterion
     backward -> openglue_amd.optim.Adam (clip + Adam + StepLR), the constants of examples/train_fit.py
@@ -15,7 +16,7 @@ validation's pose AUC says nothing here; the precision of the ground-truth label
 frame of the batch has its own size, as MegaDepth's have; they stand for what a loader hands over after decoding.  From there to the
 parameter update every tensor stays on the GPU.
 
-    python examples/train_megadepth.py [--steps 5] [--pairs 2] [--target 320 240] [--features superpoint|sift]"""
+    python examples/train_megadepth.py [--steps 5] [--pairs 2] [--target 320 240] [--features superpoint|sift] [--augment none|weak_color_aug]"""
 import argparse
 import os
 import sys
@@ -28,7 +29,7 @@ from examples.pretrain_homography import extract, make_extractor      # noqa: E4
 from examples.train_fit import GAMMA, LR, MAX_GRAD_NORM                # noqa: E402
 from examples.train_step import MARGIN, NEG_THR, POS_THR, training_step    # noqa: E402
 from examples.validate import AUC_THR, EPI_THR, RANSAC_THR             # noqa: E402
-from openglue_amd import features, megadepth, metrics, optim, supervision, synthetic as syn    # noqa: E402
+from openglue_amd import augment, features, megadepth, metrics, optim, supervision, synthetic as syn    # noqa: E402
 from openglue_amd.superglue import SuperGlue                           # noqa: E402
 
 DEPTH = 5.0
@@ -65,7 +66,7 @@ def make_scene(B, target, dev, seed=0):
     return frames0, frames1, depth(frames0), depth(frames1), torch.stack(K0).to(dev), torch.stack(K1).to(dev), R.to(dev), torch.stack(T).to(dev)
 
 
-def run(steps=5, n_pairs=2, target=(320, 240), feature="superpoint", keypoints=512, stages=3, seed=0, log=print):
+def run(steps=5, n_pairs=2, target=(320, 240), feature="superpoint", keypoints=512, stages=3, seed=0, log=print, augmentation="none"):
     """-> ([(matched labels, total loss)] per step, the validation metrics)"""
     dev = torch.device("cuda:0")
     scene = make_scene(n_pairs, target, dev, seed)
@@ -77,9 +78,11 @@ def run(steps=5, n_pairs=2, target=(320, 240), feature="superpoint", keypoints=5
     model = model.to(dev).train()
     opt = optim.Adam(model.parameters(), lr=LR, max_grad_norm=MAX_GRAD_NORM, scheduler_gamma=GAMMA)
     gen = torch.Generator().manual_seed(seed)                  # the crop starts are drawn on the CPU
+    transform = augment.get_augmentation_transform({"name": augmentation})
+    aug_gen = torch.Generator(device=dev).manual_seed(seed)    # the augmentation on the device
     history = []
     for s in range(steps):
-        item = megadepth.megadepth_pairs(*scene, target, random_crop=True, generator=gen)
+        item = augment.augment(megadepth.megadepth_pairs(*scene, target, random_crop=True, generator=gen), transform, aug_gen)
         with torch.no_grad():
             batch = extract(extractor, item)
         opt.zero_grad(set_to_none=False)
@@ -120,5 +123,6 @@ if __name__ == "__main__":
     ap.add_argument("--target", type=int, nargs=2, default=(320, 240), metavar=("W", "H"))
     ap.add_argument("--features", default="superpoint", choices=("superpoint", "sift"))
     ap.add_argument("--keypoints", type=int, default=512)
+    ap.add_argument("--augment", default="none", choices=("none", "weak_color_aug"))
     a = ap.parse_args()
-    run(a.steps, a.pairs, tuple(a.target), a.features, a.keypoints)
+    run(a.steps, a.pairs, tuple(a.target), a.features, a.keypoints, augmentation=a.augment)

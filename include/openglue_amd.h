@@ -902,6 +902,34 @@ int og_megadepth_features(int32_t images, int32_t tw, int32_t th, int32_t num_ke
                           const og_md_features* table_dev, float* lafs, float* scores, float* descriptors, float* depth, float* K_out,
                           void* stream);
 
+/* ABI v14, additive -- weak_color_aug (csrc/coloraug.hip): the photometric augmentation of the reference's online training step
+ * (models/matching_module.py:55-74 augment, utils/augmentations.py: kornia RandomEqualize, RandomSharpness, RandomSolarize,
+ * RandomGaussianNoise).  Device pointers only, no host synchronisation, no allocation, three launches; every result is bit-identical from
+ * run to run and independent of the batch it is computed in.  tests/coloraug_ref.py is the specification.
+ *
+ * og_color_aug: src [batch][C][H][W] float (nominally in [0, 1]) -> dst, the same shape; never in place (dst == src: OG_E_INVALID).
+ *   flags [batch] int32: bit 0 equalize, bit 1 sharpness, bit 2 solarize, bit 3 noise -- applied in that order, each only where its bit is
+ *   set; a sample with no bit set is copied.  scalars [batch][5] float = sharpness factor, solarize threshold, solarize addition, noise
+ *   mean, noise std.  seeds [batch] int64 >= 0 (8-byte aligned).  All three tables live on the device and are not read by the host.
+ *   float32, every operation rounded on its own, true divisions; clamp(t, 0, 1) = t < 0 ? 0 : t > 1 ? 1 : t (a NaN stays a NaN):
+ *     equalize, per plane:  v = x 255;  q = (v 256) / 255;  bin = q >= 255 ? 255 : q >= 0 ? (int)q : 0 (NaN: 0), idx the same of v;
+ *       h = histogram of bin, N = H W, step = (N - h[last non-empty bin]) / 255 in integers;  step == 0: y = v / 255;  else
+ *       y = (float)min(255, (sum_{j < idx} h[j] + step / 2) / step) / 255.
+ *     sharpness, pixels with 0 < x < W - 1 and 0 < y < H - 1 (the others keep the input):  blur = clamp of the nine taps summed in
+ *       row-major order, weights (float)(1 / 13) and, at the centre, (float)(5 / 13);  factor 0: blur;  factor 1: the input;  else
+ *       blur + (in - blur) factor, clamped unless 0 < factor < 1.
+ *     solarize:  t = clamp(x + addition, 0, 1);  t < threshold ? t : 1 - t.
+ *     noise:  i = (c H + y) W + x;  h = mix64(mix64(seed) + i) with mix64(z): z += 0x9E3779B97F4A7C15, z = (z ^ z >> 30) 0xBF58476D1CE4E5B9,
+ *       z = (z ^ z >> 27) 0x94D049BB133111EB, z ^ z >> 31 (uint64, wrapping);  u1 = ((h >> 40) + 1) 2^-24, u2 = ((h >> 16) & 0xFFFFFF) 2^-24;
+ *       z = sqrtf(-2 logf(u1)) cosf(6.2831855f u2);  out = x + (mean + std z), not clamped.
+ *   workspace_dev: og_color_aug_workspace_bytes(batch, C, H, W) bytes, 4-byte aligned, contents irrelevant on entry.
+ *   Limits: 1 <= batch <= 65535, 1 <= H, W <= 32768, C in {1, 3}, workspace_bytes large enough, else OG_E_SHAPE; a null pointer
+ *   OG_E_INVALID; a table, image or workspace not 4-byte aligned (seeds: 8) OG_E_ALIGN -- all before anything is launched.
+ * og_color_aug_workspace_bytes: 0 for a shape og_color_aug refuses. */
+size_t og_color_aug_workspace_bytes(int32_t batch, int32_t C, int32_t H, int32_t W);
+int og_color_aug(int32_t batch, int32_t C, int32_t H, int32_t W, const float* src, float* dst, const int32_t* flags, const float* scalars,
+                 const int64_t* seeds, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -223,6 +223,8 @@ SYMBOLS = {
     "og_resize_f32": (C.c_int, [_i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "og_megadepth_pairs": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "og_megadepth_features": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_color_aug_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
+    "og_color_aug": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -14,8 +14,8 @@ integer bilinear weights that sum to 2^15 -- and the kernels are bit-identical t
 run to run and whatever the batch.  cv2 itself evaluates the coordinates block-wise, so its last bit can differ.
 
 Out of scope: JPEG decoding and cv2.resize(..., INTER_AREA) to `resize_shape` are the loader's job, frames arrive as uint8 tensors;
-the albumentations colour augmentation of oxford_paris_dataset.py:18-22 and kornia's weak_color_aug are not applied, so
-homography_pairs equals the reference with the augmentation's probabilities at 0.
+the albumentations colour augmentation of oxford_paris_dataset.py:18-22 is not applied, so homography_pairs equals the reference
+with that augmentation's probabilities at 0.  kornia's weak_color_aug of the training step is openglue_amd.augment.
 """
 from __future__ import annotations
 
