@@ -18,7 +18,8 @@
 //                forward used.  Per-tile fp32 partials (128 pixels), combined in tile order in float64.
 //   dz           formed on load (sp_bn_dz) for the weight and data gradients: dz = scale (gy - dbeta / N - xhat dgamma / N), dense at
 //                full resolution also where the pool routed gy to one pixel in four.
-//   wgrad/dgrad  the MFMA bodies of superpoint_train.hip with these loaders; the layer's input x is sp_bn_act of the layer below.
+//   wgrad/dgrad  the kernels and the layer loop of og_superpoint_train.h, which SuperPointNet runs too, instantiated with these loaders
+//                (the policy SpBn); the layer's input x is sp_bn_act of the layer below.
 //                The convolution biases get no gradient here: the mean subtraction removes them (the caller returns exact zeros).
 #include "og_superpoint_train.h"
 
@@ -28,9 +29,6 @@ constexpr int SPB_LAYERS = SP_LAYERS + 1;                                   // B
 constexpr int kBnC[SPB_LAYERS] = {64, 64, 64, 64, 128, 128, 128, 128, 512};
 constexpr int SPB_CHANNELS = 1280;                                          // sum of kBnC
 constexpr int SPB_TILE = 128;                                               // pixels per flat tile (conv1a statistics, backward reductions)
-constexpr int SPB_TARGET_WGS = 512;                                         // weight-gradient split, as superpoint_train.hip
-constexpr int64_t SPB_1A_PIX = 1024;                                        // pixels per conv1a weight-gradient workgroup, as superpoint_train.hip
-Split wgrad_split(int B, int h, int w, int Cin, int Cout) { return sp_wgrad_split(B, h, w, Cin, Cout, SPB_TARGET_WGS); }
 int bn_offset(int L) {
     int o = 0;
     for (int i = 0; i < L; ++i) o += kBnC[i];
@@ -131,6 +129,38 @@ __device__ __forceinline__ f32x4 sp_bn_dz(const float* __restrict__ g, const flo
     for (int e = 0; e < 4; ++e) out[e] = sp_bn_dz1(gy[e], zv[e], s[e], mu[e], k1[e], k2[e]);
     return out;
 }
+
+// SuperPointNetBn for the kernels of og_superpoint_train.h: the gradient is dz formed on load, the layer's input sp_bn_act of the raw
+// map below (through its pool, where there is one).  The data gradient is that of the input ACTIVATION, stored unmasked: the ReLU mask
+// and the pool routing of the layer below are applied where that layer's gy is formed.  No bias gradient.
+struct SpBn {
+    struct Grad {
+        const float *g, *z;          // the gradient of the layer's activation; the layer's raw output
+        SpBnCoef k;
+    };
+    struct In {
+        const float *z, *cf;         // the raw map of the layer below [B][Hz][Wz][Cin] and its forward coefficients
+        int Hz, Wz;
+    };
+    static constexpr bool kBias = false, kPoolOnLoad = true, kDump1a = true;
+    template <bool POOLED>
+    static __device__ __forceinline__ f32x4 grad_at(const Grad& s, int b, int H, int W, int C, int y, int x, int c) {
+        return sp_bn_dz<POOLED>(s.g, s.z, s.k, b, H, W, C, y, x, c);
+    }
+    template <bool INPOOL>
+    static __device__ __forceinline__ f32x4 input_at(const In& s, int b, int H, int W, int C, int y, int x, int c) {
+        return sp_bn_act_at<INPOOL>(s.z, s.cf, b, s.Hz, s.Wz, C, y, x, c);
+    }
+    static __device__ __forceinline__ auto grad1a(const Grad& s, int co) {          // bn1a is not pooled
+        const float sc = s.k.sc[co], be = s.k.be[co], mu = s.k.mu[co], k1 = s.k.k1[co], k2 = s.k.k2[co];
+        return [=, g = s.g, z = s.z](int64_t p) {
+            const float zv = z[p * 64 + co];
+            const float gy = sp_bn_act(zv, mu, sc, be) > 0.f ? g[p * 64 + co] : 0.f;
+            return sp_bn_dz1(gy, zv, sc, mu, k1, k2);
+        };
+    }
+    static __device__ __forceinline__ float dx_value(const In&, int64_t, float v) { return v; }
+};
 
 // ---------------------------------------------------------------- forward: conv1a raw, with statistics partials
 // Workgroup = SPB_TILE consecutive pixels of B * H * W; thread (c4 = tid & 15, slot = tid >> 4) takes every 16th pixel.
@@ -431,160 +461,6 @@ __global__ __launch_bounds__(256) void sp_bn_reduce_finish_kernel(const float* _
     }
 }
 
-// debug: dz of a layer as every kernel below sees it, out [B][H][W][C]
-template <bool POOLED>
-__global__ __launch_bounds__(256) void sp_bn_dz_dump_kernel(const float* __restrict__ g, const float* __restrict__ z, SpBnCoef k, int B, int H,
-                                                            int W, int C, float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c4 = C / 4;
-    if (t >= (int64_t)B * H * W * c4) return;
-    const int c = (int)(t % c4) * 4;
-    const int64_t p = t / c4;
-    const int x = (int)(p % W), y = (int)((p / W) % H), b = (int)(p / ((int64_t)W * H));
-    *reinterpret_cast<f32x4*>(out + p * C + c) = sp_bn_dz<POOLED>(g, z, k, b, H, W, C, y, x, c);
-}
-
-// ---------------------------------------------------------------- backward: data gradient
-// dx [B][H][W][Cx] = conv3x3(dz, W^T flipped): the gradient of the layer's input ACTIVATION, unmasked -- the ReLU mask and the pool routing
-// of the layer below are applied where that layer's gy is formed.  Sums as sp_dgrad_kernel (one accumulator per pass of 32 channels).
-template <int BN, bool POOLED>
-__global__ __launch_bounds__(256, 2) void sp_bn_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ z, SpBnCoef k,
-                                                             const float* __restrict__ wp, int B, int H, int W, int Cg, int Cx,
-                                                             float* __restrict__ dx) {
-    constexpr int TM = 2, TN = BN / 64;
-    __shared__ __attribute__((aligned(16))) float tile[SP_HALO_H * SP_HALO_W * SP_LDSC];
-    const SpTile t = sp_tile(H, W, BN);
-    const int b = t.b, lane = t.lane;
-    f32x16 acc[TM][TN];
-    sp_conv3x3_accumulate<BN, true>([=](int gy, int gx, int c) { return sp_bn_dz<POOLED>(g, z, k, b, H, W, Cg, gy, gx, c); }, wp, H, W, Cg, t, tile,
-                                    acc);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int co = t.n0 + t.wn * (BN / 2) + j * 32 + (lane & 31);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int band = t.ty0 + 4 * t.wm + 2 * i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = mfma32_row(r, lane);
-                const int y = band + (m >> 4), x = t.tx0 + (m & 15);
-                if (y >= H || x >= W) continue;
-                dx[(((int64_t)b * H + y) * W + x) * Cx + co] = acc[i][j][r];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------- backward: weight gradient, split over pixel tiles
-// The tiling, MFMA sequence and reductions of sp_wgrad_kernel; A = dz formed on load, B = the layer's input activation formed on load
-// from the raw map below (xz [B][Hz][Wz][Cin], its forward coefficients xcf).  part_w [S][Cout][Cin][9].
-template <bool POOLED, bool INPOOL>
-__global__ __launch_bounds__(256) void sp_bn_wgrad_kernel(const float* __restrict__ g, const float* __restrict__ z, SpBnCoef k,
-                                                          const float* __restrict__ xz, const float* __restrict__ xcf, int B, int H, int W, int Hz, int Wz, int Cin, int Cout,
-                                                          int tiles_per, float* __restrict__ part_w) {
-    __shared__ __attribute__((aligned(16))) float gl[SP_TH * SP_TW * SPW_LD];
-    __shared__ __attribute__((aligned(16))) float xl[SP_HALO_H * SP_HALO_W * SPW_LD];      // also the 4 x 1024 floats of the wave reduction
-    static_assert(SP_HALO_H * SP_HALO_W * SPW_LD >= 4 * 1024, "the wave reduction reuses the halo tile");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int s = blockIdx.x, ci_tiles = Cin / 32;
-    const int co0 = ((int)blockIdx.y / ci_tiles) * 32, ci0 = ((int)blockIdx.y % ci_tiles) * 32;
-    const int tiles_x = (W + SP_TW - 1) / SP_TW, tiles_y = (H + SP_TH - 1) / SP_TH;
-    const int total = B * tiles_y * tiles_x;
-    const int t_begin = s * tiles_per, t_end = min(total, t_begin + tiles_per);
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tap][r] = 0.f;
-
-    for (int t = t_begin; t < t_end; ++t) {
-        int id = t;
-        const int tx0 = (id % tiles_x) * SP_TW;
-        id /= tiles_x;
-        const int ty0 = (id % tiles_y) * SP_TH;
-        const int b = id / tiles_y;
-        __syncthreads();
-        for (int f = tid; f < SP_TH * SP_TW * 8; f += 256) {
-            const int q = f & 7, p = f >> 3;
-            const int y = ty0 + (p >> 4), xx = tx0 + (p & 15);
-            f32x4 v{0.f, 0.f, 0.f, 0.f};
-            if (y < H && xx < W) v = sp_bn_dz<POOLED>(g, z, k, b, H, W, Cout, y, xx, co0 + q * 4);
-            *reinterpret_cast<f32x4*>(&gl[p * SPW_LD + q * 4]) = v;
-        }
-        for (int f = tid; f < SP_HALO_H * SP_HALO_W * 8; f += 256) {
-            const int q = f & 7, p = f >> 3;
-            const int py = p / SP_HALO_W, px = p - py * SP_HALO_W;
-            const int gy = ty0 - 1 + py, gx = tx0 - 1 + px;
-            f32x4 v{0.f, 0.f, 0.f, 0.f};
-            if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = sp_bn_act_at<INPOOL>(xz, xcf, b, Hz, Wz, Cin, gy, gx, ci0 + q * 4);
-            *reinterpret_cast<f32x4*>(&xl[p * SPW_LD + q * 4]) = v;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int kk = 0; kk < 16; ++kk) {
-            const int prow = 2 * wave + (kk >> 3), pcol = 2 * (kk & 7) + (lane >> 5);
-            const float av = gl[(prow * SP_TW + pcol) * SPW_LD + (lane & 31)];
-            const float* xb = &xl[(prow * SP_HALO_W + pcol) * SPW_LD + (lane & 31)];
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
-                acc[tap] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, xb[((tap / 3) * SP_HALO_W + (tap % 3)) * SPW_LD], acc[tap], 0, 0, 0);
-        }
-    }
-
-    // the four waves in wave order, one tap at a time through LDS
-    float* red = xl;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[wave * 1024 + r * 64 + lane] = acc[tap][r];
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int e = tid + 256 * u;
-            const float v = ((red[e] + red[1024 + e]) + red[2048 + e]) + red[3072 + e];
-            const int co = co0 + mfma32_row(e >> 6, e & 63), ci = ci0 + (e & 31);
-            part_w[(((int64_t)s * Cout + co) * Cin + ci) * 9 + tap] = v;
-        }
-    }
-}
-
-// conv1a: dW[co][tap] = sum over pixels of dz[p][co] img[p + tap], as sp_wgrad1a_kernel with dz of bn1a formed on load (not pooled)
-__global__ __launch_bounds__(256) void sp_bn_wgrad1a_kernel(const float* __restrict__ g, const float* __restrict__ z, SpBnCoef k,
-                                                            const float* __restrict__ img, int B, int H, int W, int64_t pix_per,
-                                                            float* __restrict__ part_w) {
-    __shared__ float red[4][64][9];
-    const int tid = threadIdx.x, co = tid & 63, sub = tid >> 6;
-    const int64_t total = (int64_t)B * H * W;
-    const int64_t p0 = (int64_t)blockIdx.x * pix_per, p1 = min(total, p0 + pix_per);
-    const float sc = k.sc[co], be = k.be[co], mu = k.mu[co], k1 = k.k1[co], k2 = k.k2[co];
-    float acc[9];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) acc[i] = 0.f;
-    for (int64_t p = p0 + sub; p < p1; p += 4) {
-        const int x = (int)(p % W), y = (int)((p / W) % H);
-        const float* im = img + (p / ((int64_t)W * H)) * H * W;
-        const float zv = z[p * 64 + co];
-        const float gy = sp_bn_act(zv, mu, sc, be) > 0.f ? g[p * 64 + co] : 0.f;
-        const float gv = sp_bn_dz1(gy, zv, sc, mu, k1, k2);
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-            const float v = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? im[(int64_t)yy * W + xx] : 0.f;
-            acc[tap] = __builtin_fmaf(gv, v, acc[tap]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) red[sub][co][i] = acc[i];
-    __syncthreads();
-    if (tid < 64) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i)
-            part_w[((int64_t)blockIdx.x * 64 + tid) * 9 + i] = ((red[0][tid][i] + red[1][tid][i]) + red[2][tid][i]) + red[3][tid][i];
-    }
-}
-
 // ---------------------------------------------------------------- host side
 // Saved (floats): hidden [npix][512] activated first, so that the caller can view it; the forward coefficients of the nine layers
 // (4 C each); z1a; z[j] of the eight MFMA layers at the resolution they convolve at.
@@ -612,33 +488,25 @@ BnSaved bn_saved_layout(int B, int H, int W) {
     return S;
 }
 
-int conv_tiles(int B, int h, int w) { return B * ((h + SP_TH - 1) / SP_TH) * ((w + SP_TW - 1) / SP_TW); }
 int flat_tiles(int B, int h, int w) { return (int)(((int64_t)B * h * w + SPB_TILE - 1) / SPB_TILE); }
 
 // Workspace (floats), forward and backward: the statistics [C][T][3] / reduction [C][T][2] partials of the largest layer, the backward
 // coefficients k1 | k2, the two data-gradient buffers and the weight-gradient partials.
 struct BnWs {
-    int64_t stat, kb, buf_even, buf_odd, part, total;
+    int64_t stat, kb;
+    BackwardWs bwd;
 };
 BnWs bn_ws_layout(int B, int H, int W) {
-    const Dims d = dims(H, W);
     BnWs w{};
-    int64_t o = 0;
     int64_t stat = (int64_t)64 * flat_tiles(B, H, W) * 3;
-    int64_t part = (((int64_t)B * H * W + SPB_1A_PIX - 1) / SPB_1A_PIX) * 64 * 9;
     for (int j = 0; j < SP_LAYERS; ++j) {
         int h, ww;
         layer_dims(j, H, W, h, ww);
         stat = std::max(stat, (int64_t)kCout[j] * std::max(conv_tiles(B, h, ww), flat_tiles(B, h, ww)) * 3);
-        const Split sp = wgrad_split(B, h, ww, kCin[j], kCout[j]);
-        part = std::max(part, (int64_t)sp.S * kCout[j] * kCin[j] * 9);
     }
-    w.stat = o; o += og_round_up(stat, 64);
-    w.kb = o; o += og_round_up(2 * 512, 64);
-    w.buf_even = o; o += og_round_up((int64_t)B * H * W * 64, 64);
-    w.buf_odd = o; o += og_round_up(std::max((int64_t)B * d.H2 * d.W2 * 64, (int64_t)B * d.Hc * d.Wc * 128), 64);
-    w.part = o; o += og_round_up(part, 64);
-    w.total = o;
+    w.stat = 0;
+    w.kb = og_round_up(stat, 64);
+    w.bwd = backward_layout(w.kb + og_round_up(2 * 512, 64), B, H, W, false);
     return w;
 }
 
@@ -661,10 +529,31 @@ void bn_conv(const float* zin, const float* cf, const float* w, const float* bia
                        Hz, Wz, Cin, Cout, zout, part);
 }
 
-template <int BN, bool POOLED>
-void bn_dgrad(const float* g, const float* z, const SpBnCoef& k, const float* wp, int B, int H, int W, int Cg, int Cx, float* dx, hipStream_t st) {
-    hipLaunchKernelGGL((sp_bn_dgrad_kernel<BN, POOLED>), dim3(conv_tiles(B, H, W), Cx / BN), dim3(256), 0, st, g, z, k, wp, B, H, W, Cg, Cx, dx);
-}
+// what backward_layers asks of the network.  grad: dbeta, dgamma (into bn_grads) and the backward coefficients of BatchNorm layer L from
+// the gradient g of its activation, launched ahead of the layer's kernels, which then form dz on load.
+struct BnBackward {
+    int B, H, W;
+    const float* A;                                  // the saved buffer
+    BnSaved S;
+    float *stat, *kb, *bn_grads;
+    hipStream_t st;
+    SpBn::Grad grad(int L, const float* g, int h, int w) const {
+        const int C = kBnC[L], T = flat_tiles(B, h, w), o = bn_offset(L);
+        const float* z = L == 0 ? A + S.z1a : A + S.z[L - 1];
+        const float* cf = A + S.coef + 4 * o;
+        const SpBnCoef k = bn_coef(cf, nullptr, C);
+        if (L > 0 && kPooled[L - 1]) hipLaunchKernelGGL(sp_bn_reduce_kernel<true>, dim3(T), dim3(256), 0, st, g, z, k, B, h, w, C, stat);
+        else hipLaunchKernelGGL(sp_bn_reduce_kernel<false>, dim3(T), dim3(256), 0, st, g, z, k, B, h, w, C, stat);
+        hipLaunchKernelGGL(sp_bn_reduce_finish_kernel, dim3(C), dim3(256), 0, st, stat, T, (double)B * h * w, cf, C, bn_grads + o,
+                           bn_grads + SPB_CHANNELS + o, kb);
+        return {g, z, bn_coef(cf, kb, C)};
+    }
+    SpBn::In input(int j) const {                    // the raw map below layer j, at the resolution it was convolved at, and its coefficients
+        int hz = H, wz = W;
+        if (j > 0) layer_dims(j - 1, H, W, hz, wz);
+        return {j == 0 ? A + S.z1a : A + S.z[j - 1], A + S.coef + 4 * bn_offset(j), hz, wz};
+    }
+};
 
 }  // namespace
 
@@ -675,7 +564,7 @@ extern "C" size_t og_superpoint_bn_train_saved_bytes(int32_t batch, int32_t H, i
 
 extern "C" size_t og_superpoint_bn_train_workspace_bytes(int32_t batch, int32_t H, int32_t W) {
     if (!bn_shape_ok(batch, H, W)) return 0;
-    return (size_t)bn_ws_layout(batch, H, W).total * 4 + 256;
+    return (size_t)bn_ws_layout(batch, H, W).bwd.total * 4 + 256;
 }
 
 extern "C" int og_superpoint_bn_train_forward(int32_t batch, int32_t H, int32_t W, const float* image, const void* packed_dev,
@@ -746,89 +635,11 @@ extern "C" int og_superpoint_bn_train_backward(int32_t batch, int32_t H, int32_t
     if ((uintptr_t)packed_grad_dev % 16 || (uintptr_t)saved_dev % 16 || (uintptr_t)g_hidden % 16 || (uintptr_t)workspace_dev % 16 ||
         (uintptr_t)layer_grads % 16)
         return OG_E_ALIGN;
-    const SpLayout L = sp_layout();                  // grads: as og_superpoint_train_backward; the bias slots are left untouched
-    const BnSaved S = bn_saved_layout(batch, H, W);
     const BnWs Wk = bn_ws_layout(batch, H, W);
-    const float* A = (const float*)saved_dev;
-    const float* coef = A + S.coef;
-    const float* PG = (const float*)packed_grad_dev;
     float* ws = (float*)workspace_dev;
-    float *part = ws + Wk.part, *stat = ws + Wk.stat, *kb = ws + Wk.kb;
-    float *dgamma = bn_grads, *dbeta = bn_grads + SPB_CHANNELS;
-    hipStream_t st = (hipStream_t)stream;
-
-    // dbeta, dgamma and the backward coefficients of BatchNorm layer Lb from the gradient g of its activation
-    auto reduce = [&](int Lb, const float* g, const float* z, int h, int w, bool pooled) {
-        const int C = kBnC[Lb], T = flat_tiles(batch, h, w);
-        const float* cf = coef + 4 * bn_offset(Lb);
-        const SpBnCoef k = bn_coef(cf, nullptr, C);
-        if (pooled) hipLaunchKernelGGL(sp_bn_reduce_kernel<true>, dim3(T), dim3(256), 0, st, g, z, k, batch, h, w, C, stat);
-        else hipLaunchKernelGGL(sp_bn_reduce_kernel<false>, dim3(T), dim3(256), 0, st, g, z, k, batch, h, w, C, stat);
-        hipLaunchKernelGGL(sp_bn_reduce_finish_kernel, dim3(C), dim3(256), 0, st, stat, T, (double)batch * h * w, cf, C, dgamma + bn_offset(Lb),
-                           dbeta + bn_offset(Lb), kb);
-        return bn_coef(cf, kb, C);
-    };
-
-    const float* g = g_hidden;
-    for (int j = SP_LAYERS - 1; j >= 0 && j + 1 >= first_layer; --j) {
-        int h, w, hz = H, wz = W;
-        layer_dims(j, H, W, h, w);
-        if (j > 0) layer_dims(j - 1, H, W, hz, wz);
-        const int Cin = kCin[j], Cout = kCout[j];
-        const float* z = A + S.z[j];
-        const SpBnCoef k = reduce(j + 1, g, z, h, w, kPooled[j]);
-        const bool inpool = j > 0 && kPooled[j - 1];
-        const float* xz = j == 0 ? A + S.z1a : A + S.z[j - 1];
-        const float* cx = coef + 4 * bn_offset(j);
-        const Split sp = wgrad_split(batch, h, w, Cin, Cout);
-        const int64_t nw = (int64_t)Cout * Cin * 9;
-        const dim3 grid(sp.S, (Cin / 32) * (Cout / 32));
-        if (kPooled[j]) {                                                   // a pooled layer's input is never pooled (a-layers sit between)
-            hipLaunchKernelGGL((sp_bn_wgrad_kernel<true, false>), grid, dim3(256), 0, st, g, z, k, xz, cx, batch, h, w, hz, wz, Cin, Cout,
-                               sp.tiles_per, part);
-        } else if (inpool) {
-            hipLaunchKernelGGL((sp_bn_wgrad_kernel<false, true>), grid, dim3(256), 0, st, g, z, k, xz, cx, batch, h, w, hz, wz, Cin, Cout,
-                               sp.tiles_per, part);
-        } else {
-            hipLaunchKernelGGL((sp_bn_wgrad_kernel<false, false>), grid, dim3(256), 0, st, g, z, k, xz, cx, batch, h, w, hz, wz, Cin, Cout,
-                               sp.tiles_per, part);
-        }
-        reduce_parts(part, sp.S, nw, grads + L.w[j], st);
-        if (layer_grads) {
-            int64_t off = (int64_t)batch * H * W * 64;                       // bn1a's dz first, then the eight layers
-            for (int i = 0; i < j; ++i) {
-                int hi, wi;
-                layer_dims(i, H, W, hi, wi);
-                off += (int64_t)batch * hi * wi * kCout[i];
-            }
-            const int64_t nt = (int64_t)batch * h * w * (Cout / 4);
-            const dim3 dgrid((unsigned)((nt + 255) / 256));
-            if (kPooled[j]) hipLaunchKernelGGL(sp_bn_dz_dump_kernel<true>, dgrid, dim3(256), 0, st, g, z, k, batch, h, w, Cout, layer_grads + off);
-            else hipLaunchKernelGGL(sp_bn_dz_dump_kernel<false>, dgrid, dim3(256), 0, st, g, z, k, batch, h, w, Cout, layer_grads + off);
-        }
-        if (j < first_layer) break;                  // nothing below needs a gradient
-        float* dx = ws + (j % 2 == 0 ? Wk.buf_even : Wk.buf_odd);
-        const float* wp = PG + dgrad_offset(j);
-        if (Cin == 64 || conv_tiles(batch, h, w) < 512) {                   // as og_superpoint_train_backward
-            if (kPooled[j]) bn_dgrad<64, true>(g, z, k, wp, batch, h, w, Cout, Cin, dx, st);
-            else bn_dgrad<64, false>(g, z, k, wp, batch, h, w, Cout, Cin, dx, st);
-        } else {
-            if (kPooled[j]) bn_dgrad<128, true>(g, z, k, wp, batch, h, w, Cout, Cin, dx, st);
-            else bn_dgrad<128, false>(g, z, k, wp, batch, h, w, Cout, Cin, dx, st);
-        }
-        g = dx;
-    }
-    if (first_layer == 0) {
-        const SpBnCoef k = reduce(0, g, A + S.z1a, H, W, false);
-        const int64_t total = (int64_t)batch * H * W;
-        const int S1 = (int)((total + SPB_1A_PIX - 1) / SPB_1A_PIX);
-        hipLaunchKernelGGL(sp_bn_wgrad1a_kernel, dim3(S1), dim3(256), 0, st, g, A + S.z1a, k, image, batch, H, W, SPB_1A_PIX, part);
-        reduce_parts(part, S1, 64 * 9, grads + L.w1a, st);
-        if (layer_grads) {
-            const int64_t nt = total * 16;
-            hipLaunchKernelGGL(sp_bn_dz_dump_kernel<false>, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, g, A + S.z1a, k, batch, H, W, 64,
-                               layer_grads);
-        }
-    }
+    BnBackward net{batch, H, W, (const float*)saved_dev, bn_saved_layout(batch, H, W), ws + Wk.stat, ws + Wk.kb, bn_grads, (hipStream_t)stream};
+    // grads: as og_superpoint_train_backward; the bias slots are left untouched
+    backward_layers<SpBn>(net, batch, H, W, image, (const float*)packed_grad_dev, g_hidden, first_layer, grads, layer_grads, ws, Wk.bwd,
+                          (hipStream_t)stream);
     return og_launch_status();
 }

@@ -19,13 +19,11 @@
 //   wgrad1a      conv1a has one input channel: 64 x 9 sums over all pixels on the VALU, same two stages.
 //   describe     backward of sample_desc_from_points + F.normalize: one wave per keypoint writes dv, its cell and its four weights;
 //                then one wave per coarse cell gathers from the keypoints that touch it, in keypoint order.
+// dgrad, wgrad, wgrad1a, the dump kernel and the loop over the layers live in og_superpoint_train.h, which SuperPointNetBn runs too;
+// this unit instantiates them with the policy SpPlain.
 #include "og_superpoint_train.h"
 
 namespace {
-
-constexpr int SPW_TARGET_WGS = 512;                  // workgroups a weight-gradient launch aims at (two per CU)
-constexpr int64_t SP_1A_PIX = 1024;                  // pixels per conv1a weight-gradient workgroup
-Split wgrad_split(int B, int h, int w, int Cin, int Cout) { return sp_wgrad_split(B, h, w, Cin, Cout, SPW_TARGET_WGS); }
 
 // ---------------------------------------------------------------- forward of a pooled layer that also keeps the unpooled activation
 // out = pool(relu(conv + b)) exactly as sp_conv3x3_kernel<BN, true> (max over the window, then bias and ReLU); pre = relu(conv + b) at
@@ -101,168 +99,29 @@ __device__ __forceinline__ f32x4 sp_grad_at(const float* __restrict__ g, const f
     }
 }
 
-// debug: the full-resolution pre-activation gradient of a layer as every kernel below sees it, out [B][H][W][C]
-template <bool POOLED>
-__global__ __launch_bounds__(256) void sp_grad_dump_kernel(const float* __restrict__ g, const float* __restrict__ a, int B, int H, int W, int C,
-                                                           float* __restrict__ out) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int c4 = C / 4;
-    if (t >= (int64_t)B * H * W * c4) return;
-    const int c = (int)(t % c4) * 4;
-    const int64_t p = t / c4;
-    const int x = (int)(p % W), y = (int)((p / W) % H), b = (int)(p / ((int64_t)W * H));
-    *reinterpret_cast<f32x4*>(out + p * C + c) = sp_grad_at<POOLED>(g, a, b, H, W, C, y, x, c);
-}
-
-// ---------------------------------------------------------------- data gradient of a 3x3 layer
-// dx [B][H][W][Cx] = conv3x3(G, W^T flipped) masked by xin > 0 (xin: the layer's input = the post-ReLU output of the layer below, same
-// shape as dx).  Cg = the layer's output channels (the K axis here), wp = the layer's block of the dgrad blob (og_superpoint_train_pack).
-template <int BN, bool POOLED>
-__global__ __launch_bounds__(256, 2) void sp_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ a,
-                                                          const float* __restrict__ wp, const float* __restrict__ xin, int B, int H, int W,
-                                                          int Cg, int Cx, float* __restrict__ dx) {
-    constexpr int TM = 2, TN = BN / 64;
-    __shared__ __attribute__((aligned(16))) float tile[SP_HALO_H * SP_HALO_W * SP_LDSC];
-    const SpTile t = sp_tile(H, W, BN);
-    const int b = t.b, lane = t.lane;
-    f32x16 acc[TM][TN];
-    sp_conv3x3_accumulate<BN, true>([=](int gy, int gx, int c) { return sp_grad_at<POOLED>(g, a, b, H, W, Cg, gy, gx, c); }, wp, H, W, Cg, t, tile, acc);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-        const int co = t.n0 + t.wn * (BN / 2) + j * 32 + (lane & 31);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int band = t.ty0 + 4 * t.wm + 2 * i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = mfma32_row(r, lane);
-                const int y = band + (m >> 4), x = t.tx0 + (m & 15);
-                if (y >= H || x >= W) continue;
-                const int64_t o = (((int64_t)b * H + y) * W + x) * Cx + co;
-                dx[o] = xin[o] > 0.f ? acc[i][j][r] : 0.f;
-            }
-        }
+// SuperPointNet for the kernels of og_superpoint_train.h: G through sp_grad_at, the layer's input as it was saved (post-ReLU), the data
+// gradient masked by that input > 0, and a bias gradient.
+struct SpPlain {
+    struct Grad {
+        const float *g, *a;          // the gradient at the layer's output resolution; the activation before the pool (pooled layers)
+    };
+    struct In {
+        const float* x;
+    };
+    static constexpr bool kBias = true, kPoolOnLoad = false, kDump1a = false;
+    template <bool POOLED>
+    static __device__ __forceinline__ f32x4 grad_at(const Grad& s, int b, int H, int W, int C, int y, int x, int c) {
+        return sp_grad_at<POOLED>(s.g, s.a, b, H, W, C, y, x, c);
     }
-}
-
-// ---------------------------------------------------------------- weight and bias gradient of a 3x3 layer, split over pixel tiles
-// Workgroup (split s, block (co0, ci0)): tiles [s * tiles_per, (s + 1) * tiles_per) of the B * tiles_y * tiles_x pixel tiles.
-// MFMA: D[co][ci] += A[co][k] B[k][ci] with k a pixel pair: lane l gives A = G[pixel 2 kk + (l >> 5)][co0 + (l & 31)] and, per tap,
-// B = x[that pixel + tap][ci0 + (l & 31)].  part_w [S][Cout][Cin][9], part_b [S][Cout] (written by the ci0 == 0 workgroups).
-template <bool POOLED>
-__global__ __launch_bounds__(256) void sp_wgrad_kernel(const float* __restrict__ g, const float* __restrict__ a, const float* __restrict__ x,
-                                                       int B, int H, int W, int Cin, int Cout, int tiles_per, float* __restrict__ part_w,
-                                                       float* __restrict__ part_b) {
-    __shared__ __attribute__((aligned(16))) float gl[SP_TH * SP_TW * SPW_LD];
-    __shared__ __attribute__((aligned(16))) float xl[SP_HALO_H * SP_HALO_W * SPW_LD];      // also the 4 x 1024 floats of the wave reduction
-    __shared__ float bl[4][32];
-    static_assert(SP_HALO_H * SP_HALO_W * SPW_LD >= 4 * 1024, "the wave reduction reuses the halo tile");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int s = blockIdx.x, ci_tiles = Cin / 32;
-    const int co0 = ((int)blockIdx.y / ci_tiles) * 32, ci0 = ((int)blockIdx.y % ci_tiles) * 32;
-    const int tiles_x = (W + SP_TW - 1) / SP_TW, tiles_y = (H + SP_TH - 1) / SP_TH;
-    const int total = B * tiles_y * tiles_x;
-    const int t_begin = s * tiles_per, t_end = min(total, t_begin + tiles_per);
-
-    f32x16 acc[9];
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[tap][r] = 0.f;
-    float bsum = 0.f;
-
-    for (int t = t_begin; t < t_end; ++t) {
-        int id = t;
-        const int tx0 = (id % tiles_x) * SP_TW;
-        id /= tiles_x;
-        const int ty0 = (id % tiles_y) * SP_TH;
-        const int b = id / tiles_y;
-        __syncthreads();
-        for (int f = tid; f < SP_TH * SP_TW * 8; f += 256) {
-            const int q = f & 7, p = f >> 3;
-            const int y = ty0 + (p >> 4), xx = tx0 + (p & 15);
-            f32x4 v{0.f, 0.f, 0.f, 0.f};
-            if (y < H && xx < W) v = sp_grad_at<POOLED>(g, a, b, H, W, Cout, y, xx, co0 + q * 4);
-            *reinterpret_cast<f32x4*>(&gl[p * SPW_LD + q * 4]) = v;
-        }
-        for (int f = tid; f < SP_HALO_H * SP_HALO_W * 8; f += 256) {
-            const int q = f & 7, p = f >> 3;
-            const int py = p / SP_HALO_W, px = p - py * SP_HALO_W;
-            const int gy = ty0 - 1 + py, gx = tx0 - 1 + px;
-            f32x4 v{0.f, 0.f, 0.f, 0.f};
-            if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = *reinterpret_cast<const f32x4*>(x + (((int64_t)b * H + gy) * W + gx) * Cin + ci0 + q * 4);
-            *reinterpret_cast<f32x4*>(&xl[p * SPW_LD + q * 4]) = v;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int kk = 0; kk < 16; ++kk) {
-            const int prow = 2 * wave + (kk >> 3), pcol = 2 * (kk & 7) + (lane >> 5);
-            const float av = gl[(prow * SP_TW + pcol) * SPW_LD + (lane & 31)];
-            bsum += av;
-            const float* xb = &xl[(prow * SP_HALO_W + pcol) * SPW_LD + (lane & 31)];
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap)
-                acc[tap] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, xb[((tap / 3) * SP_HALO_W + (tap % 3)) * SPW_LD], acc[tap], 0, 0, 0);
-        }
+    template <bool INPOOL>
+    static __device__ __forceinline__ f32x4 input_at(const In& s, int b, int H, int W, int C, int y, int x, int c) {
+        return *reinterpret_cast<const f32x4*>(s.x + (((int64_t)b * H + y) * W + x) * C + c);
     }
-
-    // the four waves in wave order, one tap at a time through LDS
-    float* red = xl;
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 16; ++r) red[wave * 1024 + r * 64 + lane] = acc[tap][r];
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int e = tid + 256 * u;
-            const float v = ((red[e] + red[1024 + e]) + red[2048 + e]) + red[3072 + e];
-            const int co = co0 + mfma32_row(e >> 6, e & 63), ci = ci0 + (e & 31);
-            part_w[(((int64_t)s * Cout + co) * Cin + ci) * 9 + tap] = v;
-        }
+    static __device__ __forceinline__ auto grad1a(const Grad& s, int co) {
+        return [g = s.g, co](int64_t p) { return g[p * 64 + co]; };
     }
-    bsum += __shfl_xor(bsum, 32, 64);
-    if (lane < 32) bl[wave][lane] = bsum;
-    __syncthreads();
-    if (ci0 == 0 && tid < 32) part_b[(int64_t)s * Cout + co0 + tid] = ((bl[0][tid] + bl[1][tid]) + bl[2][tid]) + bl[3][tid];
-}
-
-// conv1a: dW[co][tap] = sum over pixels of G[p][co] img[p + tap], db[co] = sum of G[p][co].  Workgroup s owns pixels
-// [s * pix_per, (s + 1) * pix_per) of B * H * W; thread (co = tid & 63, sub = tid >> 6) walks every fourth pixel of the range.
-__global__ __launch_bounds__(256) void sp_wgrad1a_kernel(const float* __restrict__ g, const float* __restrict__ img, int B, int H, int W,
-                                                         int64_t pix_per, float* __restrict__ part_w, float* __restrict__ part_b) {
-    __shared__ float red[4][64][10];
-    const int tid = threadIdx.x, co = tid & 63, sub = tid >> 6;
-    const int64_t total = (int64_t)B * H * W;
-    const int64_t p0 = (int64_t)blockIdx.x * pix_per, p1 = min(total, p0 + pix_per);
-    float acc[10];
-#pragma unroll
-    for (int i = 0; i < 10; ++i) acc[i] = 0.f;
-    for (int64_t p = p0 + sub; p < p1; p += 4) {
-        const int x = (int)(p % W), y = (int)((p / W) % H);
-        const float* im = img + (p / ((int64_t)W * H)) * H * W;
-        const float gv = g[p * 64 + co];
-        acc[9] += gv;
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            const int yy = y + tap / 3 - 1, xx = x + tap % 3 - 1;
-            const float v = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? im[(int64_t)yy * W + xx] : 0.f;
-            acc[tap] = fmaf(gv, v, acc[tap]);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 10; ++i) red[sub][co][i] = acc[i];
-    __syncthreads();
-    if (tid < 64) {
-#pragma unroll
-        for (int i = 0; i < 10; ++i) {
-            const float v = ((red[0][tid][i] + red[1][tid][i]) + red[2][tid][i]) + red[3][tid][i];
-            if (i < 9) part_w[((int64_t)blockIdx.x * 64 + tid) * 9 + i] = v;
-            else part_b[(int64_t)blockIdx.x * 64 + tid] = v;
-        }
-    }
-}
+    static __device__ __forceinline__ float dx_value(const In& s, int64_t o, float v) { return s.x[o] > 0.f ? v : 0.f; }
+};
 
 // ---------------------------------------------------------------- backward of describe (bilinear sample + F.normalize)
 // The four taps of a keypoint, as sp_describe_kernel computes them: cell (y0, x0) and its right / lower neighbours, weights nw ne sw se.
@@ -386,41 +245,20 @@ Saved saved_layout(int B, int H, int W) {
     return S;
 }
 
-
-struct BackwardWs {
-    int64_t buf_even, buf_odd, part, total;          // floats
-};
-BackwardWs backward_layout(int B, int H, int W) {
-    const Dims d = dims(H, W);
-    BackwardWs w{};
-    int64_t o = 0;
-    w.buf_even = o; o += og_round_up((int64_t)B * H * W * 64, 64);
-    const int64_t odd = std::max((int64_t)B * d.H2 * d.W2 * 64, (int64_t)B * d.Hc * d.Wc * 128);
-    w.buf_odd = o; o += og_round_up(odd, 64);
-    int64_t part = (((int64_t)B * H * W + SP_1A_PIX - 1) / SP_1A_PIX) * 64 * 10;
-    for (int j = 0; j < SP_LAYERS; ++j) {
-        int h, ww;
-        layer_dims(j, H, W, h, ww);
-        const Split sp = wgrad_split(B, h, ww, kCin[j], kCout[j]);
-        part = std::max(part, (int64_t)sp.S * ((int64_t)kCout[j] * kCin[j] * 9 + kCout[j]));
-    }
-    w.part = o; o += og_round_up(part, 64);
-    w.total = o;
-    return w;
-}
-
 template <int BN>
 void conv_save(const float* in, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout, float* out, float* pre,
                hipStream_t st) {
-    const int tiles = ((W + SP_TW - 1) / SP_TW) * ((H + SP_TH - 1) / SP_TH) * B;
-    hipLaunchKernelGGL((sp_conv3x3_save_kernel<BN>), dim3(tiles, Cout / BN), dim3(256), 0, st, in, w, bias, B, H, W, Cin, Cout, out, pre);
+    hipLaunchKernelGGL((sp_conv3x3_save_kernel<BN>), dim3(conv_tiles(B, H, W), Cout / BN), dim3(256), 0, st, in, w, bias, B, H, W, Cin, Cout,
+                       out, pre);
 }
 
-template <int BN, bool POOLED>
-void dgrad(const float* g, const float* a, const float* wp, const float* xin, int B, int H, int W, int Cg, int Cx, float* dx, hipStream_t st) {
-    const int tiles = ((W + SP_TW - 1) / SP_TW) * ((H + SP_TH - 1) / SP_TH) * B;
-    hipLaunchKernelGGL((sp_dgrad_kernel<BN, POOLED>), dim3(tiles, Cx / BN), dim3(256), 0, st, g, a, wp, xin, B, H, W, Cg, Cx, dx);
-}
+// what backward_layers asks of the network: G of a layer as the chain hands it over, routed through the saved pre-pool activation
+struct PlainBackward {
+    const float* A;
+    Saved S;
+    SpPlain::Grad grad(int L, const float* g, int, int) const { return {g, L > 0 && kPooled[L - 1] ? A + S.pre[L - 1] : nullptr}; }
+    SpPlain::In input(int j) const { return {j == 0 ? A + S.a1a : A + S.act[j - 1]}; }
+};
 
 }  // namespace
 
@@ -461,7 +299,7 @@ extern "C" size_t og_superpoint_train_saved_bytes(int32_t batch, int32_t H, int3
 
 extern "C" size_t og_superpoint_train_workspace_bytes(int32_t batch, int32_t H, int32_t W, int32_t n) {
     if (!dense_shape_ok(batch, H, W) || n < 0) return 0;
-    const size_t bwd = (size_t)backward_layout(batch, H, W).total * 4;
+    const size_t bwd = (size_t)backward_layout(0, batch, H, W, true).total * 4;
     const size_t desc = (size_t)og_round_up((int64_t)batch * n * (SP_D + 8) * 4, 256);
     return std::max(bwd, desc) + 256;
 }
@@ -503,65 +341,9 @@ extern "C" int og_superpoint_train_backward(int32_t batch, int32_t H, int32_t W,
     if ((uintptr_t)packed_grad_dev % 16 || (uintptr_t)saved_dev % 16 || (uintptr_t)g_hidden % 16 || (uintptr_t)workspace_dev % 16 ||
         (uintptr_t)layer_grads % 16)
         return OG_E_ALIGN;
-    const SpLayout L = sp_layout();                  // grads: the natural-order twin of the packed layout (w1a [64][9], b1a, w[j] [Cout][Cin][9], b[j])
-    const Saved S = saved_layout(batch, H, W);
-    const BackwardWs Wk = backward_layout(batch, H, W);
-    const float* A = (const float*)saved_dev;
-    const float* PG = (const float*)packed_grad_dev;
-    float* ws = (float*)workspace_dev;
-    float* part = ws + Wk.part;
-    hipStream_t st = (hipStream_t)stream;
-
-    const float* g = g_hidden;
-    for (int j = SP_LAYERS - 1; j >= 0 && j + 1 >= first_layer; --j) {
-        int h, w;
-        layer_dims(j, H, W, h, w);
-        const int Cin = kCin[j], Cout = kCout[j];
-        const float* x = j == 0 ? A + S.a1a : A + S.act[j - 1];              // the layer's input
-        const float* a = kPooled[j] ? A + S.pre[j] : nullptr;
-        const Split sp = wgrad_split(batch, h, w, Cin, Cout);
-        const int64_t nw = (int64_t)Cout * Cin * 9;
-        float* part_b = part + (int64_t)sp.S * nw;
-        const dim3 grid(sp.S, (Cin / 32) * (Cout / 32));
-        if (kPooled[j]) hipLaunchKernelGGL(sp_wgrad_kernel<true>, grid, dim3(256), 0, st, g, a, x, batch, h, w, Cin, Cout, sp.tiles_per, part, part_b);
-        else hipLaunchKernelGGL(sp_wgrad_kernel<false>, grid, dim3(256), 0, st, g, a, x, batch, h, w, Cin, Cout, sp.tiles_per, part, part_b);
-        reduce_parts(part, sp.S, nw, grads + L.w[j], st);
-        reduce_parts(part_b, sp.S, Cout, grads + L.b[j], st);
-        if (layer_grads) {
-            int64_t off = 0;
-            for (int i = 0; i < j; ++i) {
-                int hi, wi;
-                layer_dims(i, H, W, hi, wi);
-                off += (int64_t)batch * hi * wi * kCout[i];
-            }
-            const int64_t nt = (int64_t)batch * h * w * (Cout / 4);
-            const dim3 dgrid((unsigned)((nt + 255) / 256));
-            if (kPooled[j]) hipLaunchKernelGGL(sp_grad_dump_kernel<true>, dgrid, dim3(256), 0, st, g, a, batch, h, w, Cout, layer_grads + off);
-            else hipLaunchKernelGGL(sp_grad_dump_kernel<false>, dgrid, dim3(256), 0, st, g, a, batch, h, w, Cout, layer_grads + off);
-        }
-        if (j < first_layer) break;                  // nothing below needs a gradient
-        float* dx = ws + (j % 2 == 0 ? Wk.buf_even : Wk.buf_odd);
-        const float* wp = PG + dgrad_offset(j);
-        // 128 output channels per workgroup only where the pixel tiles alone fill the chip: at coarse resolution (38 tiles at 480 x 640)
-        // two workgroups of 64 channels halve the serial MFMA chain of a wave.  The sums per output are the same either way.
-        const int tiles = batch * ((h + SP_TH - 1) / SP_TH) * ((w + SP_TW - 1) / SP_TW);
-        if (Cin == 64 || tiles < 512) {
-            if (kPooled[j]) dgrad<64, true>(g, a, wp, x, batch, h, w, Cout, Cin, dx, st);
-            else dgrad<64, false>(g, a, wp, x, batch, h, w, Cout, Cin, dx, st);
-        } else {
-            if (kPooled[j]) dgrad<128, true>(g, a, wp, x, batch, h, w, Cout, Cin, dx, st);
-            else dgrad<128, false>(g, a, wp, x, batch, h, w, Cout, Cin, dx, st);
-        }
-        g = dx;
-    }
-    if (first_layer == 0) {
-        const int64_t total = (int64_t)batch * H * W;
-        const int S1 = (int)((total + SP_1A_PIX - 1) / SP_1A_PIX);
-        float* part_b = part + (int64_t)S1 * 64 * 9;
-        hipLaunchKernelGGL(sp_wgrad1a_kernel, dim3(S1), dim3(256), 0, st, g, image, batch, H, W, SP_1A_PIX, part, part_b);
-        reduce_parts(part, S1, 64 * 9, grads + L.w1a, st);
-        reduce_parts(part_b, S1, 64, grads + L.b1a, st);
-    }
+    PlainBackward net{(const float*)saved_dev, saved_layout(batch, H, W)};
+    backward_layers<SpPlain>(net, batch, H, W, image, (const float*)packed_grad_dev, g_hidden, first_layer, grads, layer_grads,
+                             (float*)workspace_dev, backward_layout(0, batch, H, W, true), (hipStream_t)stream);
     return og_launch_status();
 }
 

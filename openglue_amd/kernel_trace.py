@@ -18,11 +18,11 @@ PROJ_MLP = ("mlp_small_kernel<", "mlp_fused_kernel<", "proj_small_kernel<", "pro
 ATTENTION_TRAIN = ("attention_bwd_kernel<", "attention_lse_kernel<", "attention_delta_kernel")     # csrc/attention_train.hip
 SINKHORN = ("sinkhorn_sweep_kernel<", "sinkhorn_sweep_fast_kernel<", "sinkhorn_combine_kernel<", "sinkhorn_combine_fast_kernel<", "sinkhorn_scores_kernel<",
             "sinkhorn_resident_kernel<", "sinkhorn_fallback_kernel<")     # csrc/sinkhorn.hip, csrc/sinkhorn_resident.hip: the inference Sinkhorn
-SUPERPOINT_TRAIN = ("sp_conv3x3_save_kernel<", "sp_dgrad_kernel<", "sp_wgrad_kernel<", "sp_wgrad1a_kernel", "sp_reduce_parts_kernel", "sp_describe_bwd_point_kernel",
-                    "sp_describe_bwd_cell_kernel", "sp_grad_dump_kernel<")     # csrc/superpoint_train.hip: the SuperPoint fine-tuning kernels
+SUPERPOINT_TRAIN = ("sp_conv3x3_save_kernel<", "sp_dgrad_kernel<SpPlain,", "sp_wgrad_kernel<SpPlain,", "sp_wgrad1a_kernel<SpPlain>", "sp_reduce_parts_kernel", "sp_describe_bwd_point_kernel",
+                    "sp_describe_bwd_cell_kernel", "sp_grad_dump_kernel<SpPlain,")     # csrc/superpoint_train.hip: the SuperPoint fine-tuning kernels (the shared bodies of csrc/og_superpoint_train.h as SpPlain)
 SUPERPOINT_BN_TRAIN = ("sp_bn_conv1a_kernel", "sp_bn_conv3x3_kernel<", "sp_bn_stats_finish_kernel", "sp_bn_act_kernel", "sp_bn_cell_tail_kernel", "sp_bn_reduce_kernel<",
-                       "sp_bn_reduce_finish_kernel", "sp_bn_dgrad_kernel<", "sp_bn_wgrad_kernel<", "sp_bn_wgrad1a_kernel", "sp_bn_dz_dump_kernel<",
-                       "sp_reduce_parts_kernel")     # csrc/superpoint_bn_train.hip: the SuperPointNetBn fine-tuning kernels
+                       "sp_bn_reduce_finish_kernel", "sp_dgrad_kernel<SpBn,", "sp_wgrad_kernel<SpBn,", "sp_wgrad1a_kernel<SpBn>", "sp_grad_dump_kernel<SpBn,",
+                       "sp_reduce_parts_kernel")     # csrc/superpoint_bn_train.hip: the SuperPointNetBn fine-tuning kernels (the shared bodies as SpBn)
 PROJ_WSTAT ="proj_wstat_kernel"       # csrc/proj_wstat.hip: the weight-stationary q | k | v projection of 256-d batches (no template arguments)
 
 

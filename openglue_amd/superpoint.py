@@ -267,6 +267,67 @@ def _softmax65_backward(logit: torch.Tensor, dp: torch.Tensor) -> torch.Tensor:
     return prob * (dp65 * rest - (pd.sum(1, keepdim=True) - pd))
 
 
+# ---- what the backward of SuperPointNet and of SuperPointNetBn share
+def _backward_result(names, need, P, grads):
+    """The tuple an autograd backward returns for (net, image, weight and bias of `names` in order): a parameter that needs a gradient
+    and received none gets zeros."""
+    out = []
+    for name in names:
+        for k in (0, 1):
+            g = grads[name][k]
+            if need[name][k] and g is None:
+                g = torch.zeros_like(P[name][k])
+            out.append(g if need[name][k] else None)
+    return (None, None, *out)
+
+
+def _detector_prelude(ops, dscores, sidx, n, hidden, conv_pb, B, Hc, Wc):
+    """From the gradient of the scores: dp [npix, 64], the gradient of the 64 kept probabilities of every cell; convPb's weight padded
+    to 68 rows (a multiple of 4, for the GEMMs); hP, convPb's input; and convPb's float64 output [npix, 65].  The logits span ~30 units
+    where the heatmap is peaked, so one fp32 ulp of a logit is already 1e-6 of a probability: the 256-term products are recomputed as 16
+    exact-fp32 GEMMs over 16 channels each and summed in float64."""
+    npix, dev = B * Hc * Wc, hidden.device
+    dheat = torch.zeros(B, Hc * 8 * Wc * 8, device=dev, dtype=torch.float32)
+    dheat.scatter_(1, sidx[:, :n].long(), dscores.to(torch.float32))                 # the kept pixels of an image are distinct
+    dp = dheat.view(B, Hc, 8, Wc, 8).permute(0, 1, 3, 2, 4).reshape(npix, 64)
+    Wp = torch.zeros(68, 256, device=dev, dtype=torch.float32)
+    Wp[:65] = conv_pb[0].detach().view(65, 256)
+    hP = hidden[:, :256].contiguous()
+    part = ops.gemm_nt(hP.view(npix, 16, 16).permute(1, 0, 2).contiguous(), Wp.view(68, 16, 16).permute(1, 0, 2).contiguous())
+    return dp, Wp, hP, part.double().sum(0)[:, :65] + conv_pb[1].detach().to(torch.float32).double()
+
+
+def _descriptor_prelude(ddesc, sidx, n, desc, nrm, ws_ptr, B, Hc, Wc):
+    """From the gradient of the sampled descriptors, through F.normalize + bilinear sampling (kernels) and the per-cell L2 norm (nrm, the
+    norm of the raw coarse descriptor): the gradient of the raw coarse descriptor [npix, 256]."""
+    npix, dev = B * Hc * Wc, desc.device
+    dd = ddesc.to(torch.float32).contiguous()
+    dcoarse = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
+    _lib.call("og_superpoint_describe_backward", dev, B, Hc, Wc, n, sidx.data_ptr(), sidx.shape[1], desc.data_ptr(), dd.data_ptr(),
+              dcoarse.data_ptr(), ws_ptr, _lib.STREAM)
+    dn, dc = desc.view(npix, 256), dcoarse.view(npix, 256)
+    return (dc - dn * (dn * dc).sum(1, keepdim=True)) / nrm
+
+
+def _layer_shapes(H, W):
+    """(h, w, C) of the gradient planes of layer_grads behind the eight MFMA layers (conv1b .. conv4b, heads)"""
+    return [(H // 2 ** s, W // 2 ** s, c) for s, c in ((0, 64), (1, 64), (1, 64), (2, 128), (2, 128), (3, 128), (3, 128), (3, 512))]
+
+
+def _conv_grad_views(flat, name):
+    """(dW, db) of CONV_NAMES entry `name` as views of the flat gradient buffer"""
+    (ow, sw), (ob, sb) = _GRAD_SLICES[name]
+    return flat[ow:ow + sw[0] * sw[1] * 9].view(sw), flat[ob:ob + sb[0]]
+
+
+def _layer_grad_views(dbg, names, shapes, B):
+    out, o = {}, 0
+    for name, (h, w, c) in zip(names, shapes):
+        out[name] = dbg[o:o + B * h * w * c].view(B, h, w, c)
+        o += B * h * w * c
+    return out
+
+
 class _SuperPointTrain(torch.autograd.Function):
     """SuperPointNet.forward with a backward.  Inputs: the module, the image, then weight and bias of CONV_NAMES in order."""
 
@@ -303,46 +364,25 @@ class _SuperPointTrain(torch.autograd.Function):
         P = {name: (params[2 * i], params[2 * i + 1]) for i, name in enumerate(CONV_NAMES)}
         dev = img.device
         grads = {name: [None, None] for name in CONV_NAMES}
-
-        def result():
-            out = []
-            for name in CONV_NAMES:
-                for k in (0, 1):
-                    g = grads[name][k]
-                    if need[name][k] and g is None:
-                        g = torch.zeros_like(P[name][k])
-                    out.append(g if need[name][k] else None)
-            return (None, None, *out)
-
         if n == 0:                                   # no keypoint: every gradient is zero, nothing to launch
-            return result()
+            return _backward_result(CONV_NAMES, need, P, grads)
         Hc, Wc = H // 8, W // 8
         npix = B * Hc * Wc
         hidden = saved[:npix * 512].view(npix, 512)
         ws = torch.empty(_lib.load().og_superpoint_train_workspace_bytes(B, H, W, n), device=dev, dtype=torch.uint8)
+        ws_ptr = ws.data_ptr() + (-ws.data_ptr()) % 256
         trunk_first = next((i for i, name in enumerate(_TRUNK) if any(need[name])), 8)
         need_hidden = trunk_first < 8 or any(need["convPa"]) or any(need["convDa"])
         g_hidden = torch.zeros(npix, 512, device=dev, dtype=torch.float32)
 
         # ---- detector head: scores are heatmap values at the kept pixels -> softmax over 65 -> convPb
         if dscores is not None and (need_hidden or any(need["convPb"])):
-            dheat = torch.zeros(B, Hc * 8 * Wc * 8, device=dev, dtype=torch.float32)
-            dheat.scatter_(1, sidx[:, :n].long(), dscores.to(torch.float32))         # the kept pixels of an image are distinct
-            dp = dheat.view(B, Hc, 8, Wc, 8).permute(0, 1, 3, 2, 4).reshape(npix, 64)
-            Wp = torch.zeros(68, 256, device=dev, dtype=torch.float32)               # 65 rows padded to a multiple of 4 for the GEMMs
-            Wp[:65] = P["convPb"][0].detach().view(65, 256)
-            bp = torch.zeros(68, device=dev, dtype=torch.float32)
-            bp[:65] = P["convPb"][1].detach()
-            hP = hidden[:, :256].contiguous()
+            dp, Wp, hP, logit = _detector_prelude(ops, dscores, sidx, n, hidden, P["convPb"], B, Hc, Wc)
             # softmax backward, dlogit_c = p_c (dp_c - s) with s = sum_k p_k dp_k, written so that a peaked cell does not cancel: a kept
             # pixel is a local maximum, often with p_c close to 1, where dp_c - s = dp_c (1 - p_c) - (s - p_c dp_c) loses every digit in
             # the textbook form.  1 - p_c = (the sum of the OTHER exponentials) / Z comes from an exclusive prefix and suffix sum (all
-            # terms positive); s - p_c dp_c is exactly 0 when the cell holds one keypoint.
-            # The logits span ~30 units where the heatmap is peaked, so one fp32 ulp of a logit is already 1e-6 of a probability: the
-            # 256-term products are recomputed as 16 exact-fp32 GEMMs over 16 channels each and summed, like everything that follows
-            # up to dlog, in float64 tensor algebra at coarse resolution.
-            part = ops.gemm_nt(hP.view(npix, 16, 16).permute(1, 0, 2).contiguous(), Wp.view(68, 16, 16).permute(1, 0, 2).contiguous())
-            logit = part.double().sum(0)[:, :65] + bp[:65].double()
+            # terms positive); s - p_c dp_c is exactly 0 when the cell holds one keypoint.  Like the logits, everything up to dlog is
+            # float64 tensor algebra at coarse resolution.
             dlog = torch.zeros(npix, 68, device=dev, dtype=torch.float32)
             dlog[:, :65] = _softmax65_backward(logit, dp.double())
             dh, dW, db = train._conv_backward(hP, Wp, dlog, need_hidden, any(need["convPb"]))
@@ -353,15 +393,10 @@ class _SuperPointTrain(torch.autograd.Function):
 
         # ---- descriptor head: F.normalize + bilinear sampling (kernels) -> per-cell L2 norm -> convDb
         if ddesc is not None and (need_hidden or any(need["convDb"])):
-            dd = ddesc.to(torch.float32).contiguous()
-            dcoarse = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
-            _lib.call("og_superpoint_describe_backward", dev, B, Hc, Wc, n, sidx.data_ptr(), sidx.shape[1], desc.data_ptr(), dd.data_ptr(),
-                      dcoarse.data_ptr(), ws.data_ptr() + (-ws.data_ptr()) % 256, _lib.STREAM)
             Wd, bd = P["convDb"][0].detach().view(256, 256).contiguous(), P["convDb"][1].detach()
             hD = hidden[:, 256:].contiguous()
             nrm = torch.linalg.vector_norm(ops.gemm_nt(hD, Wd, bd), dim=1, keepdim=True)
-            dn, dc = desc.view(npix, 256), dcoarse.view(npix, 256)
-            draw = (dc - dn * (dn * dc).sum(1, keepdim=True)) / nrm
+            draw = _descriptor_prelude(ddesc, sidx, n, desc, nrm, ws_ptr, B, Hc, Wc)
             dh, dW, db = train._conv_backward(hD, Wd, draw, need_hidden, any(need["convDb"]))
             if any(need["convDb"]):
                 grads["convDb"] = [dW.reshape(256, 256, 1, 1), db]
@@ -372,23 +407,15 @@ class _SuperPointTrain(torch.autograd.Function):
         if need_hidden:
             g_hidden = g_hidden * (hidden > 0)       # ReLU of convPa | convDa
             flat = torch.empty(_GRAD_FLOATS, device=dev, dtype=torch.float32)
-            dbg = None
-            if net.keep_layer_grads:
-                lv = [(H, W, 64), (H // 2, W // 2, 64), (H // 2, W // 2, 64), (H // 4, W // 4, 128), (H // 4, W // 4, 128),
-                      (Hc, Wc, 128), (Hc, Wc, 128), (Hc, Wc, 512)]
-                dbg = torch.zeros(sum(B * h * w * c for h, w, c in lv), device=dev, dtype=torch.float32)
+            shapes = _layer_shapes(H, W)
+            dbg = torch.zeros(sum(B * h * w * c for h, w, c in shapes), device=dev, dtype=torch.float32) if net.keep_layer_grads else None
             _lib.call("og_superpoint_train_backward", dev, B, H, W, img.data_ptr(), net._pack_grad(dev).data_ptr(), saved.data_ptr(),
-                      g_hidden.data_ptr(), trunk_first, flat.data_ptr(), _lib.ptr(dbg), ws.data_ptr() + (-ws.data_ptr()) % 256, _lib.STREAM)
+                      g_hidden.data_ptr(), trunk_first, flat.data_ptr(), _lib.ptr(dbg), ws_ptr, _lib.STREAM)
             for name in _TRUNK[trunk_first:] + ["convPa", "convDa"]:
-                (ow, sw), (ob, sb) = _GRAD_SLICES[name]
-                nw = sw[0] * sw[1] * 9
-                grads[name] = [flat[ow:ow + nw].view(sw), flat[ob:ob + sb[0]]]
+                grads[name] = list(_conv_grad_views(flat, name))
             if dbg is not None:
-                net.layer_grads, o = {}, 0
-                for name, (h, w, c) in zip(_TRUNK[1:] + ["heads"], lv):
-                    net.layer_grads[name] = dbg[o:o + B * h * w * c].view(B, h, w, c)
-                    o += B * h * w * c
-        return result()
+                net.layer_grads = _layer_grad_views(dbg, _TRUNK[1:] + ["heads"], shapes, B)
+        return _backward_result(CONV_NAMES, need, P, grads)
 
 
 _BN_TRUNK = BN_NAMES[:8] + ["bnPa", "bnDa"]         # the modules og_superpoint_bn_train_forward normalises with, in its order
@@ -465,20 +492,10 @@ class _SuperPointBnTrain(torch.autograd.Function):
         need = {name: (ctx.needs_input_grad[2 + 2 * i], ctx.needs_input_grad[3 + 2 * i]) for i, name in enumerate(names)}
         P = {name: (params[2 * i], params[2 * i + 1]) for i, name in enumerate(names)}
         dev = img.device
+        # a convolution bias that needs a gradient receives zeros: the mean subtraction removes it, its gradient is exactly 0
         grads = {name: [None, None] for name in names}
-
-        def result():
-            out = []
-            for name in names:
-                for k in (0, 1):
-                    g = grads[name][k]
-                    if need[name][k] and g is None:  # also every convolution bias: the mean subtraction removes it, its gradient is exactly 0
-                        g = torch.zeros_like(P[name][k])
-                    out.append(g if need[name][k] else None)
-            return (None, None, *out)
-
         if n == 0:                                   # no keypoint: every gradient is zero, nothing to launch
-            return result()
+            return _backward_result(names, need, P, grads)
         Hc, Wc = H // 8, W // 8
         npix = B * Hc * Wc
         hidden = saved[:npix * 512].view(npix, 512)
@@ -487,17 +504,9 @@ class _SuperPointBnTrain(torch.autograd.Function):
         need_hidden = trunk_first < 8 or wants("convPa", "convDa", "bnPa", "bnDa")
         g_hidden = torch.zeros(npix, 512, device=dev, dtype=torch.float32)
 
-        # ---- detector head: scores -> softmax over 65 -> bnPb -> convPb, in float64 tensor algebra at coarse resolution from logits
-        # recomputed as 16 exact-fp32 GEMMs over 16 channels each (as _SuperPointTrain.backward, and for its reason)
+        # ---- detector head: scores -> softmax over 65 -> bnPb -> convPb, in float64 tensor algebra at coarse resolution
         if dscores is not None and (need_hidden or wants("convPb", "bnPb")):
-            dheat = torch.zeros(B, Hc * 8 * Wc * 8, device=dev, dtype=torch.float32)
-            dheat.scatter_(1, sidx[:, :n].long(), dscores.to(torch.float32))
-            dp = dheat.view(B, Hc, 8, Wc, 8).permute(0, 1, 3, 2, 4).reshape(npix, 64)
-            Wp = torch.zeros(68, 256, device=dev, dtype=torch.float32)
-            Wp[:65] = P["convPb"][0].detach().view(65, 256)
-            hP = hidden[:, :256].contiguous()
-            part = ops.gemm_nt(hP.view(npix, 16, 16).permute(1, 0, 2).contiguous(), Wp.view(68, 16, 16).permute(1, 0, 2).contiguous())
-            z = part.double().sum(0)[:, :65] + P["convPb"][1].detach().double()
+            dp, Wp, hP, z = _detector_prelude(ops, dscores, sidx, n, hidden, P["convPb"], B, Hc, Wc)
             gam, bet = P["bnPb"][0].detach().double(), P["bnPb"][1].detach().double()
             r = torch.rsqrt(z.var(0, unbiased=False) + float(net.bnPb.eps))
             xh = (z - z.mean(0)) * r
@@ -514,13 +523,8 @@ class _SuperPointBnTrain(torch.autograd.Function):
 
         # ---- descriptor head: F.normalize + bilinear sampling (kernels) -> per-cell L2 norm -> bnDb (og_batchnorm_train_backward) -> convDb
         if ddesc is not None and (need_hidden or wants("convDb", "bnDb")):
-            dd = ddesc.to(torch.float32).contiguous()
-            dcoarse = torch.empty(B, Hc, Wc, 256, device=dev, dtype=torch.float32)
             wsd = _lib.workspace(B * n * 264 * 4 + 256, dev)
-            _lib.call("og_superpoint_describe_backward", dev, B, Hc, Wc, n, sidx.data_ptr(), sidx.shape[1], desc.data_ptr(), dd.data_ptr(),
-                      dcoarse.data_ptr(), wsd[1], _lib.STREAM)
-            dn, dc = desc.view(npix, 256), dcoarse.view(npix, 256)
-            dy = ((dc - dn * (dn * dc).sum(1, keepdim=True)) / nrm).contiguous()
+            dy = _descriptor_prelude(ddesc, sidx, n, desc, nrm, wsd[1], B, Hc, Wc).contiguous()
             dz = torch.empty_like(dy)
             dgamma = torch.empty(256, device=dev, dtype=torch.float32)
             dbeta = torch.empty(256, device=dev, dtype=torch.float32)
@@ -539,26 +543,19 @@ class _SuperPointBnTrain(torch.autograd.Function):
         if need_hidden:
             flat = torch.empty(_GRAD_FLOATS, device=dev, dtype=torch.float32)
             bnflat = torch.zeros(2, 1280, device=dev, dtype=torch.float32)
-            dbg = None
-            lv = [(H, W, 64), (H, W, 64), (H // 2, W // 2, 64), (H // 2, W // 2, 64), (H // 4, W // 4, 128), (H // 4, W // 4, 128),
-                  (Hc, Wc, 128), (Hc, Wc, 128), (Hc, Wc, 512)]
-            if net.keep_layer_grads:
-                dbg = torch.zeros(sum(B * h * w * c for h, w, c in lv), device=dev, dtype=torch.float32)
+            shapes = [(H, W, 64)] + _layer_shapes(H, W)                              # bn1a's dz first
+            dbg = torch.zeros(sum(B * h * w * c for h, w, c in shapes), device=dev, dtype=torch.float32) if net.keep_layer_grads else None
             wsbuf = _lib.workspace(_lib.load().og_superpoint_bn_train_workspace_bytes(B, H, W), dev)
             _lib.call("og_superpoint_bn_train_backward", dev, B, H, W, img.data_ptr(), net._pack_grad(dev).data_ptr(), saved.data_ptr(),
                       g_hidden.data_ptr(), trunk_first, flat.data_ptr(), bnflat.data_ptr(), _lib.ptr(dbg), wsbuf[1], _lib.STREAM)
             for name in _TRUNK[trunk_first:] + ["convPa", "convDa"]:
-                (ow, sw), _ = _GRAD_SLICES[name]
-                grads[name][0] = flat[ow:ow + sw[0] * sw[1] * 9].view(sw)
+                grads[name][0] = _conv_grad_views(flat, name)[0]
             for name in _BN_TRUNK[trunk_first:]:
                 o, c = _BN_OFFSETS[name], getattr(net, name).num_features
                 grads[name] = [bnflat[0, o:o + c], bnflat[1, o:o + c]]
             if dbg is not None:
-                net.layer_grads, o = {}, 0
-                for name, (h, w, c) in zip(_TRUNK + ["heads"], lv):
-                    net.layer_grads[name] = dbg[o:o + B * h * w * c].view(B, h, w, c)
-                    o += B * h * w * c
-        return result()
+                net.layer_grads = _layer_grad_views(dbg, _TRUNK + ["heads"], shapes, B)
+        return _backward_result(names, need, P, grads)
 
 
 class SuperPointNetBn(SuperPointNet):

@@ -1,8 +1,8 @@
-"""Cases and float64 references for the per-kernel tests of csrc/superpoint_train.hip (tests/test_superpoint_train_cases_cpu.py checks this
+"""Cases and float64 references for the per-kernel tests of csrc/superpoint_train.hip and the bodies it takes from csrc/og_superpoint_train.h (tests/test_superpoint_train_cases_cpu.py checks this
 file against the library and torch autograd on the CPU; tests/test_gpu_superpoint_train_forms.py runs the kernels against it).
 
 Everything here is plain torch on the CPU.  The launcher's arithmetic is restated (saved_layout, wgrad_split, dgrad_form, launch_list);
-its constants -- SPW_TARGET_WGS, the `tiles < 512` rule of the data gradient, SP_1A_PIX -- are read out of the .hip source, so that a
+its constants -- SPW_TARGET_WGS, the `tiles < 512` rule of the data gradient, SP_1A_PIX -- are read out of the shared header, so that a
 changed constant fails test_case_properties instead of silently moving a case off the launch form it was chosen for.
 
 Layers are the eight MFMA layers j = 0..7 of the source (conv1b, 2a, 2b, 3a, 3b, 4a, 4b, heads Pa | Da); conv1a is "conv1a".
@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from torch.nn.grad import conv2d_input, conv2d_weight
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = os.path.join(ROOT, "openglue_amd", "csrc", "superpoint_train.hip")
+SOURCE = os.path.join(ROOT, "openglue_amd", "csrc", "og_superpoint_train.h")       # the launcher both SuperPoint training units share
 LAYERS = [(64, 64), (64, 64), (64, 64), (64, 128), (128, 128), (128, 128), (128, 128), (128, 512)]       # (Cin, Cout)
 POOLED = (True, False, True, False, True, False, False, False)
 SHIFT = (0, 1, 1, 2, 2, 3, 3, 3)                     # layer j convolves at (H >> SHIFT[j], W >> SHIFT[j])
@@ -77,19 +77,20 @@ def layers_run(first_layer):
 
 
 def launch_list(B, H, W, first_layer, dump=True):
-    """the kernels of one og_superpoint_train_backward call, in launch order, by their short names"""
+    """the kernels of one og_superpoint_train_backward call, in launch order, by their short names (SpPlain: SuperPointNet's instances of
+    the bodies in og_superpoint_train.h; the third argument of sp_wgrad_kernel, INPOOL, is always false for this network)"""
     b = lambda v: "true" if v else "false"
     out = []
     for j in layers_run(first_layer):
         h, w = layer_dims(j, H, W)
-        out += [f"sp_wgrad_kernel<{b(POOLED[j])}>", "sp_reduce_parts_kernel", "sp_reduce_parts_kernel"]
+        out += [f"sp_wgrad_kernel<SpPlain, {b(POOLED[j])}, false>", "sp_reduce_parts_kernel", "sp_reduce_parts_kernel"]
         if dump:
-            out.append(f"sp_grad_dump_kernel<{b(POOLED[j])}>")
+            out.append(f"sp_grad_dump_kernel<SpPlain, {b(POOLED[j])}>")
         if j >= first_layer:
             bn, pooled = dgrad_form(j, tiles(B, h, w))
-            out.append(f"sp_dgrad_kernel<{bn}, {b(pooled)}>")
+            out.append(f"sp_dgrad_kernel<SpPlain, {bn}, {b(pooled)}>")
     if first_layer == 0:
-        out += ["sp_wgrad1a_kernel", "sp_reduce_parts_kernel", "sp_reduce_parts_kernel"]
+        out += ["sp_wgrad1a_kernel<SpPlain>", "sp_reduce_parts_kernel", "sp_reduce_parts_kernel"]
     return out
 
 

@@ -130,8 +130,8 @@ def test_reduction_partials_on_integers():
         "og_superpoint_bn_train_backward", dev, B, H, W, gimg.data_ptr(), pg.data_ptr(), saved.data_ptr(), ggh.data_ptr(), 8, grads.data_ptr(),
         bng.data_ptr(), dump.data_ptr(), ws.data_ptr(), _lib.STREAM)))
     got = [n.replace(" ", "") for n in names]
-    assert got == ["sp_bn_reduce_kernel<false>", "sp_bn_reduce_finish_kernel", "sp_bn_wgrad_kernel<false,false>", "sp_reduce_parts_kernel",
-                   "sp_bn_dz_dump_kernel<false>"], got
+    assert got == ["sp_bn_reduce_kernel<false>", "sp_bn_reduce_finish_kernel", "sp_wgrad_kernel<SpBn,false,false>", "sp_reduce_parts_kernel",
+                   "sp_grad_dump_kernel<SpBn,false>"], got
     assert bool(ws[nws:].isnan().all()) and bool(grads[_GRAD_FLOATS:].isnan().all()) and bool(bng[2560:].isnan().all()) and \
         bool(dump[dump_n:].isnan().all())
     # float64 restatement

@@ -212,11 +212,12 @@ def test_instances():
         got = norm(_run(case, "integer")["names"])
         assert got == norm(cases.launch_list(*c)), case
         seen |= set(got)
-    layers = lambda case: [n for n in norm(_run(case, "integer")["names"]) if n.startswith("sp_dgrad_kernel<")]
-    assert layers("edge") == ["sp_dgrad_kernel<64,false>"] * 3 and layers("many")[:3] == ["sp_dgrad_kernel<128,false>"] * 3
-    assert layers("many")[3] == "sp_dgrad_kernel<128,true>"
-    want = {f"sp_dgrad_kernel<{bn},{p}>" for bn in (64, 128) for p in ("true", "false")} | \
-        {f"{k}<{p}>" for k in ("sp_wgrad_kernel", "sp_grad_dump_kernel") for p in ("true", "false")} | {"sp_wgrad1a_kernel", "sp_reduce_parts_kernel"}
+    layers = lambda case: [n for n in norm(_run(case, "integer")["names"]) if n.startswith("sp_dgrad_kernel<SpPlain,")]
+    assert layers("edge") == ["sp_dgrad_kernel<SpPlain,64,false>"] * 3 and layers("many")[:3] == ["sp_dgrad_kernel<SpPlain,128,false>"] * 3
+    assert layers("many")[3] == "sp_dgrad_kernel<SpPlain,128,true>"
+    want = {f"sp_dgrad_kernel<SpPlain,{bn},{p}>" for bn in (64, 128) for p in ("true", "false")} | \
+        {f"sp_wgrad_kernel<SpPlain,{p},false>" for p in ("true", "false")} | {f"sp_grad_dump_kernel<SpPlain,{p}>" for p in ("true", "false")} | \
+        {"sp_wgrad1a_kernel<SpPlain>", "sp_reduce_parts_kernel"}
     assert want <= seen, want - seen
 
 

@@ -129,6 +129,11 @@ def test_abi_and_sizes():
     lib = _lib.load()
     assert all(hasattr(lib, n) for n in NEW_SYMBOLS) and lib.og_abi_version() == 14
     assert "superpoint_bn_train.hip" in build.SOURCES and "sp_bn_reduce_kernel<" in kernel_trace.SUPERPOINT_BN_TRAIN
+    # the bodies shared with SuperPointNet (csrc/og_superpoint_train.h) are traced per network: neither list takes the other's instances
+    shared = ("sp_dgrad_kernel<{},", "sp_wgrad_kernel<{},", "sp_wgrad1a_kernel<{}>", "sp_grad_dump_kernel<{},")
+    assert all(s.format("SpBn") in kernel_trace.SUPERPOINT_BN_TRAIN and s.format("SpPlain") in kernel_trace.SUPERPOINT_TRAIN for s in shared)
+    assert not any(s.format("SpPlain").startswith(kernel_trace.SUPERPOINT_BN_TRAIN) or s.format("SpBn").startswith(kernel_trace.SUPERPOINT_TRAIN)
+                   for s in shared)
     assert lib.og_superpoint_bn_train_saved_bytes(1, 8, 8) == 0 and lib.og_superpoint_bn_train_workspace_bytes(1, 8, 8) == 0      # N = 1
     assert lib.og_superpoint_bn_train_saved_bytes(1, 8, 16) > 0 and lib.og_superpoint_bn_train_saved_bytes(2, 8, 8) > 0          # N = 2
     assert lib.og_superpoint_bn_train_saved_bytes(1, 7, 60) == 0 and lib.og_superpoint_bn_train_saved_bytes(1, 8192, 8193) == 0

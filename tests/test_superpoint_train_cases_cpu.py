@@ -157,8 +157,8 @@ def test_case_properties():
     assert first == 0 and all(_splits(B, H, W, j)[0] == 1 for j in range(8))
     # the predicted launch lists name all four data-gradient instances
     names = {n for c in cases.CASES.values() for n in cases.launch_list(*c)}
-    assert {f"sp_dgrad_kernel<{bn}, {p}>" for bn in (64, 128) for p in ("true", "false")} <= names
-    assert cases.launch_list(1, 8, 8, 8) == ["sp_wgrad_kernel<false>", "sp_reduce_parts_kernel", "sp_reduce_parts_kernel", "sp_grad_dump_kernel<false>"]
+    assert {f"sp_dgrad_kernel<SpPlain, {bn}, {p}>" for bn in (64, 128) for p in ("true", "false")} <= names
+    assert cases.launch_list(1, 8, 8, 8) == ["sp_wgrad_kernel<SpPlain, false, false>", "sp_reduce_parts_kernel", "sp_reduce_parts_kernel", "sp_grad_dump_kernel<SpPlain, false>"]
 
 
 @pytest.mark.parametrize("case", list(cases.CASES))
