@@ -19,30 +19,33 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
 }
 
 // Exclusive scan of a[0 .. n) in place by ONE workgroup, the total to *total_out: thread t owns ceil(n / 256) consecutive entries,
-// thread 0 scans the 256 partial sums.
+// thread 0 scans the 256 partial sums.  The entries are counts (>= 0).  The sums are kept in 64 bits and every offset and the total
+// are clamped to INT32_MAX: below 2^31 the results are the plain sums, above it they saturate instead of wrapping, so an offset
+// is never negative and a total that does not fit is still larger than any capacity the callers compare it with.
 __device__ inline void block_exclusive_scan_inplace(int32_t* __restrict__ a, int n, int32_t* __restrict__ total_out) {
-    __shared__ int32_t part[256];
+    __shared__ int64_t part[256];
+    constexpr int64_t SAT = 2147483647ll;
     const int tid = threadIdx.x;
     const int per = (n + 255) / 256;
     const int lo = min(tid * per, n), hi = min(lo + per, n);
-    int sum = 0;
+    int64_t sum = 0;
     for (int i = lo; i < hi; ++i) sum += a[i];
     part[tid] = sum;
     __syncthreads();
     if (tid == 0) {
-        int run = 0;
+        int64_t run = 0;
         for (int i = 0; i < 256; ++i) {
-            const int v = part[i];
+            const int64_t v = part[i];
             part[i] = run;
             run += v;
         }
-        *total_out = run;
+        *total_out = (int32_t)(run < SAT ? run : SAT);
     }
     __syncthreads();
-    int run = part[tid];
+    int64_t run = part[tid];
     for (int i = lo; i < hi; ++i) {
-        const int v = a[i];
-        a[i] = run;
+        const int64_t v = a[i];
+        a[i] = (int32_t)(run < SAT ? run : SAT);
         run += v;
     }
 }

@@ -424,7 +424,10 @@ __global__ __launch_bounds__(256) void sift_describe_kernel(const float* __restr
         const float obin = (atan2f(dy, dx) * 57.29577951308232f - ang0) * (8.f / 360.f);
         const float mag = sqrtf(dx * dx + dy * dy) * expf((crot * crot + rrot * rrot) * (-1.f / 8.f));
         const float r0f = floorf(rbin), c0f = floorf(cbin), o0f = floorf(obin);
-        const float fr = rbin - r0f, fc = cbin - c0f, fo = obin - o0f;
+        // obin is a product; contracted with this subtraction it is not rounded first, and where it rounds up to an integer (a
+        // gradient exactly along the keypoint's axes) the fraction comes out as -1e-7, a negative weight and, under the RootSIFT
+        // square root of the float path, a NaN.  The weights are clamped to what they mean.
+        const float fr = rbin - r0f, fc = cbin - c0f, fo = fmaxf(obin - o0f, 0.f);
         const int r0 = (int)r0f, c0 = (int)c0f, o0 = (int)o0f;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {

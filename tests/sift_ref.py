@@ -202,6 +202,64 @@ def refine(dog, cand):
     return np.concatenate(ki_out), np.concatenate(kf_out), np.concatenate(src)
 
 
+EXITS = ("converged", "det0", "big", "border", "layer", "steps")
+
+
+def refine_traced(dog, cand, max_steps=MAX_STEPS):
+    """refine() one candidate at a time, saying how each ended -> per candidate (exit, steps, (l, r, c)): exit is one of EXITS,
+    steps the number of Newton systems solved, (l, r, c) the sample it ended on (for "border" / "layer" the one it moved to and
+    never read).  max_steps other than MAX_STEPS asks what a different step limit would have done.  "converged" with steps == 1
+    is converged at once, with more it moved first; a move that leaves both the layers and the border is "layer".  The same operations in the same order as refine(), which it does not replace."""
+    out = []
+    for o, l, r, c in np.asarray(cand, dtype=np.int64).reshape(-1, 4).tolist():
+        d = np.asarray(dog[o], dtype=np.float64)
+        _, h, w = d.shape
+        end = None
+        for it in range(1, max_steps + 1):
+            v = d[l, r, c]
+            gx = 0.5 * (d[l, r, c + 1] - d[l, r, c - 1])
+            gy = 0.5 * (d[l, r + 1, c] - d[l, r - 1, c])
+            gs = 0.5 * (d[l + 1, r, c] - d[l - 1, r, c])
+            v2 = 2.0 * v
+            dxx = d[l, r, c + 1] + d[l, r, c - 1] - v2
+            dyy = d[l, r + 1, c] + d[l, r - 1, c] - v2
+            dss = d[l + 1, r, c] + d[l - 1, r, c] - v2
+            dxy = 0.25 * (d[l, r + 1, c + 1] - d[l, r + 1, c - 1] - d[l, r - 1, c + 1] + d[l, r - 1, c - 1])
+            dxs = 0.25 * (d[l + 1, r, c + 1] - d[l + 1, r, c - 1] - d[l - 1, r, c + 1] + d[l - 1, r, c - 1])
+            dys = 0.25 * (d[l + 1, r + 1, c] - d[l + 1, r - 1, c] - d[l - 1, r + 1, c] + d[l - 1, r - 1, c])
+            c00 = dyy * dss - dys * dys
+            c01 = dxs * dys - dxy * dss
+            c02 = dxy * dys - dxs * dyy
+            c11 = dxx * dss - dxs * dxs
+            c12 = dxy * dxs - dxx * dys
+            c22 = dxx * dyy - dxy * dxy
+            det = dxx * c00 + dxy * c01 + dxs * c02
+            if det == 0.0:
+                end = "det0"
+                break
+            with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+                xc = -(c00 * gx + c01 * gy + c02 * gs) / det
+                xr = -(c01 * gx + c11 * gy + c12 * gs) / det
+                xl = -(c02 * gx + c12 * gy + c22 * gs) / det
+            if abs(xc) < 0.5 and abs(xr) < 0.5 and abs(xl) < 0.5:
+                end = "converged"
+                break
+            if not abs(xc) < 1e6 or not abs(xr) < 1e6 or not abs(xl) < 1e6:
+                end = "big"
+                break
+            c += int(_round(xc))
+            r += int(_round(xr))
+            l += int(_round(xl))
+            if l < 1 or l > S:
+                end = "layer"
+                break
+            if c < BORDER or c >= w - BORDER or r < BORDER or r >= h - BORDER:
+                end = "border"
+                break
+        out.append((end or "steps", it, (l, r, c)))
+    return out
+
+
 def detect(dog):
     """DoG volume -> (ki, kf) in the order of the candidates: (octave, layer, row, column) of the extremum each started from"""
     ki, kf, _ = refine(dog, extrema(dog))
@@ -237,6 +295,24 @@ def orientation_histogram(gauss, k, size):
     b = _round(np.degrees(np.arctan2(dy, dx)) * (ORI_BINS / 360.0)).astype(np.int64) % ORI_BINS
     raw = np.bincount(b, weights=wgt * mag, minlength=ORI_BINS)
     return (np.roll(raw, 2) + np.roll(raw, -2)) * (1.0 / 16) + (np.roll(raw, 1) + np.roll(raw, -1)) * (4.0 / 16) + raw * (6.0 / 16)
+
+
+def orientation_bin_margin(gauss, k, size):
+    """smallest distance, in bins, of the angle of any non-zero gradient in keypoint k's window from a histogram bin edge (0.5 when
+    there is none): above the last-bit difference of two atan2, both sides put every sample into the same bin"""
+    o, l, r, c = (int(v) for v in k)
+    img = gauss[o][l]
+    h, w = img.shape
+    rad = int(_round(4.5 * _sigma_oct(o, size)))
+    i, j = np.meshgrid(np.arange(-rad, rad + 1), np.arange(-rad, rad + 1), indexing="ij")
+    y, x = r + i, c + j
+    m = (y > 0) & (y < h - 1) & (x > 0) & (x < w - 1)
+    dx, dy = _gradients(img, y[m], x[m])
+    nz = (dx != 0) | (dy != 0)
+    if not nz.any():
+        return 0.5
+    t = np.degrees(np.arctan2(dy[nz], dx[nz])) * (ORI_BINS / 360.0) + 0.5
+    return float(np.min(np.abs(t - np.round(t))))
 
 
 def histogram_peaks(hist):
