@@ -81,6 +81,13 @@ __device__ unsigned og_mlp_trace_buf[OG_MT_BLOCKS][8][4][64];
 #define OG_MT(k_, idx_) do {} while (0)
 #endif
 
+// What an fc.0 stage of mlp_fused_kernel knows at compile time.  CW / CX: its weight / token ring slot, NW / NX: the next stage's; -1 = the
+// run-time form (NX = -2: the next stage reads no token fragments).  RB >= 0: the residual of output block RB rides in this stage.
+// IX: the token k-group two stages ahead exists (1 / 0; -1: only if another pass follows).  XR: that k-group is k-group 0.
+template <int CW, int CX, int NW, int NX, int RB, int IX, int XR>
+struct OgFc0Stage { static constexpr int cw = CW, cx = CX, nw = NW, nx = NX, rb = RB, ix = IX, xr = XR; };
+constexpr int og_ring_wim(int slot) { return slot == 1 ? WSTAGE : 0; }      // immediate of a compile-time weight ring slot (base waA / waA / waB)
+
 template <int D>
 __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     static_assert(D == 256 || D == 128, "256-d: 8 output blocks, 2 hidden halves x 2 quarters x 4 hidden blocks, 16 k-groups; 128-d: 4 output blocks, 2 halves x 4 hidden blocks, 8 k-groups");
@@ -91,11 +98,13 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     constexpr int NPASS = HB2 / 4;            // passes of 4 hidden blocks per hidden half (256-d: the two quarters; 128-d: one)
     // fc.3 stages per pass, 16 fragments per wave each.  256-d: (hidden block j, k-step t) x 8 output blocks; 128-d: hidden block j, BOTH k-steps x 4 output blocks
     constexpr int NJT = D == 256 ? 8 : 4;
-    constexpr int STAGES = NPASS * (G0 + NJT);
-    constexpr int XSTAGES = NPASS * G0;
-    constexpr int SMEM = BOFF + (2 * D + D) * 4;
+    [[maybe_unused]] constexpr int STAGES = NPASS * (G0 + NJT);
+    [[maybe_unused]] constexpr int XSTAGES = NPASS * G0;
+    constexpr int IDOFF = BOFF + (2 * D + D) * 4;      // the residual's two identity fragments, 1 KiB each
+    constexpr int SMEM = IDOFF + 2 * 1024;
     __shared__ __attribute__((aligned(16))) char smem[SMEM];
-    static_assert(SMEM <= 163840 && 8 * 16384 <= BOFF && 2 * EPI_SLAB <= 16384, "LDS budget");
+    static_assert(SMEM <= 163840 && 8 * 16384 <= BOFF && 2 * EPI_SLAB <= 16384 && IDOFF % 16 == 0, "LDS budget");
+    static_assert(NPASS == 1 || (G0 + NJT) % 3 == 0, "every pass starts on weight ring slot 0");
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -107,12 +116,6 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     int mt_v[4] = {0, 0, 0, 0};
     OG_MT(3, 0);
 #endif
-
-    auto scalar_ptr = [](const char* p) {
-        const uint64_t v = (uint64_t)(uintptr_t)p;
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi32 = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-        return reinterpret_cast<const char*>((uintptr_t)(((uint64_t)hi32 << 32) | lo));
-    };
 
     // ---- LDS-DMA pieces (1 KiB each).  Tokens: wave w fills rows [16w, 16w+16) of a stage (2 pieces of 8 rows x 128 B); weights:
     //      wave w fills fragments [4w, 4w+4).  Every wave reads its token block's 32 rows and its hidden half's 16 fragments. ----
@@ -134,93 +137,34 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     // instruction offset applies to the global AND the LDS address), no per-piece address arithmetic.  [As builtin calls every piece
     // carried ~10 SALU + a VGPR copy + its own M0 write; LDS-DMA issue is not hidden by the other wave of the SIMD: the kernel's
     // time was matrix-pipe time + ~90 cycles x pieces per SIMD (profiles/r03_c_*).]
-    const char* const baseW = g.wstream + wave * 4 * 1024;
-#ifndef OG_MLP_BUF
-#define OG_MLP_BUF 0      // experiments: 1 = the LDS-DMA pieces as buffer_load ... lds (MUBUF) instead of global_load_lds
-#endif
-#if OG_MLP_BUF
-    typedef unsigned og_sgpr4 __attribute__((ext_vector_type(4)));
-    auto make_res = [&](const char* base, unsigned bytes) {
-        const uint64_t v = (uint64_t)(uintptr_t)base;
-        og_sgpr4 r;
-        r[0] = __builtin_amdgcn_readfirstlane((uint32_t)v);
-        r[1] = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32) & 0xFFFFu);       // stride 0
-        r[2] = __builtin_amdgcn_readfirstlane(bytes);
-        r[3] = 0x00020000u;
-        return r;
-    };
-    const og_sgpr4 resW = make_res(g.wstream, (unsigned)(STAGES * WSTAGE));
-    const og_sgpr4 resX = make_res(baseX, 0x7FFFFFFFu);
-    auto issue_w4 = [&](int s, int slot) {
-        const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)(s * WSTAGE + wave * 4096));
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + slot * WSTAGE + wave * 4096);
-        asm volatile("s_mov_b32 m0, %3\n\t"
-                     "s_nop 0\n\t"
-                     "buffer_load_dwordx4 %0, %1, %2 offen lds\n\t"
-                     "buffer_load_dwordx4 %0, %1, %2 offen offset:1024 lds\n\t"
-                     "buffer_load_dwordx4 %0, %1, %2 offen offset:2048 lds\n\t"
-                     "buffer_load_dwordx4 %0, %1, %2 offen offset:3072 lds"
-                     :: "v"(lane16), "s"(resW), "s"(so), "s"(m0v) : "memory");
-    };
-    auto issue_x2 = [&](int xs, int slot) {
-        const unsigned so = __builtin_amdgcn_readfirstlane((unsigned)((xs % G0) * 128));
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + XOFF + slot * XSTAGE + wave * 2048);
-        asm volatile("s_mov_b32 m0, %4\n\t"
-                     "s_nop 0\n\t"
-                     "buffer_load_dwordx4 %0, %2, %3 offen lds\n\t"
-                     "s_add_u32 m0, m0, 0x400\n\t"
-                     "s_nop 0\n\t"
-                     "buffer_load_dwordx4 %1, %2, %3 offen lds"
-                     :: "v"(xoff[0]), "v"(xoff[1]), "s"(resX), "s"(so), "s"(m0v) : "memory");
-    };
-#else
-    auto issue_w4 = [&](int s, int slot) {               // the 4 pieces of this wave of weight stage s into ring slot `slot`
-        const char* src = scalar_ptr(baseW + (int64_t)s * WSTAGE);
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + slot * WSTAGE + wave * 4096);
+    // The sources are SCALAR pointers that advance by scalar adds: the weight stream is consumed front to back, one stage per issue;
+    // the token k-groups go round (stage xs issues k-group (xs + 2) % G0), the stage that issues k-group 0 resets the pointer.
+    const char* wsrc = g.wstream + wave * 4 * 1024;
+    const char* xsrc = baseX;
+    const unsigned m0w = lds0 + (unsigned)(wave * 4096), m0x = lds0 + (unsigned)(XOFF + wave * 2048);
+    auto issue_w4 = [&](int slot) {                      // the 4 pieces of this wave of the next weight stage into ring slot `slot`
+        const unsigned m0v = m0w + (unsigned)(slot * WSTAGE);
         asm volatile("s_mov_b32 m0, %2\n\t"
                      "s_nop 0\n\t"
                      "global_load_lds_dwordx4 %0, %1\n\t"
                      "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
                      "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
                      "global_load_lds_dwordx4 %0, %1 offset:3072"
-                     :: "v"(lane16), "s"(src), "s"(m0v) : "memory");
+                     :: "v"(lane16), "s"(wsrc), "s"(m0v) : "memory");
+        wsrc += WSTAGE;
     };
-    auto issue_x2 = [&](int xs, int slot) {              // the 2 pieces of this wave of token stage xs (k-group xs % G0)
-        const char* src = scalar_ptr(baseX + (int64_t)(xs % G0) * 128);
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + XOFF + slot * XSTAGE + wave * 2048);
+    auto issue_x2 = [&](int slot) {                      // the 2 pieces of this wave of the next token k-group
+        const unsigned m0v = m0x + (unsigned)(slot * XSTAGE);
         asm volatile("s_mov_b32 m0, %3\n\t"
                      "s_nop 0\n\t"
                      "global_load_lds_dwordx4 %0, %2\n\t"
                      "s_add_u32 m0, m0, 0x400\n\t"
                      "s_nop 0\n\t"
                      "global_load_lds_dwordx4 %1, %2"
-                     :: "v"(xoff[0]), "v"(xoff[1]), "s"(src), "s"(m0v) : "memory");
-    };
-#ifndef OG_MLP_DMA_SPREAD
-#define OG_MLP_DMA_SPREAD 0      // experiment (round 6): the six LDS-DMA pieces of a stage one per free slot instead of 4 + 2 back to back
-#endif
-    [[maybe_unused]] auto issue_w1 = [&](int s, int slot, auto P) {      // piece p of this wave of weight stage s
-        constexpr int pce = decltype(P)::value;
-        const unsigned l16 = lane16;                           // (a plain use: asm operands alone do not capture inside a generic lambda)
-        const char* src = scalar_ptr(baseW + (int64_t)s * WSTAGE);
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + slot * WSTAGE + wave * 4096);
-        asm volatile("s_mov_b32 m0, %2\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, %1 offset:%3"
-                     :: "v"(l16), "s"(src), "s"(m0v), "n"(1024 * pce) : "memory");
-    };
-    [[maybe_unused]] auto issue_x1 = [&](int xs, int slot, auto H) {     // piece h of this wave of token stage xs
-        constexpr int hh_ = decltype(H)::value;
-        const unsigned xo = xoff[hh_];
-        const char* src = scalar_ptr(baseX + (int64_t)(xs % G0) * 128);
-        const unsigned m0v = __builtin_amdgcn_readfirstlane(lds0 + XOFF + slot * XSTAGE + wave * 2048 + hh_ * 1024);
-        asm volatile("s_mov_b32 m0, %2\n\t"
-                     "s_nop 0\n\t"
-                     "global_load_lds_dwordx4 %0, %1"
-                     :: "v"(xo), "s"(src), "s"(m0v) : "memory");
+                     :: "v"(xoff[0]), "v"(xoff[1]), "s"(xsrc), "s"(m0v) : "memory", "scc");
+        xsrc += 128;
     };
 
-#endif
 
     // ---- prologue: the bias loads first (inline asm: the compiler must not drain the DMA pieces issued behind them), then W(0), X(0),
     //      W(1), X(1); the biases * 256 go to LDS in their shadow ----
@@ -230,10 +174,22 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
         const float* p3 = g.b3 + (tid & (D - 1));
         asm volatile("global_load_dword %0, %2, off\n\tglobal_load_dword %1, %3, off" : "=&v"(bv0), "=&v"(bv3) : "v"(p0), "v"(p3) : "memory");
     }
-    issue_w4(0, 0); issue_x2(0, 0);
-    issue_w4(1, 1); issue_x2(1, 1);
+    issue_w4(0); issue_x2(0);
+    issue_w4(1); issue_x2(1);
     // accumulator multipliers of the two matrices: 1 / (power-of-two pre-scale chosen at pack time)
     const float sc0 = g.scales_dev ? g.scales_dev[0] : g.scale, sc3 = g.scales_dev ? g.scales_dev[1] : g.scale;
+    // The residual's constant A fragments "S3 x identity" of k-step t = 0, 1 (OG_RESID below) exist ONCE, in LDS behind the biases: wave t
+    // builds fragment t, the 16 bytes of lane l at IDOFF + t KiB + 16 l.  A wave only ever uses fragment t == ha: `ida` is its address.
+    unsigned ida = lds0 + (unsigned)(IDOFF + ha * 1024) + lane16;
+    asm volatile("" : "+v"(ida));
+    if (wave < 2) {
+        const _Float16 s3h = (_Float16)(1.f / sc3);           // power of two >= 2^-14 (og_weight_prescale): exact in binary16
+        const int row = l31 - 8 * hi;
+        f16x8 f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = (row == 16 * wave + e) ? s3h : (_Float16)0.f;
+        asm volatile("ds_write_b128 %0, %1" :: "v"(ida), "v"(f) : "memory");      // (inline asm, as the bias stores: not ordered behind the DMA in flight)
+    }
     {
         const float is0 = 1.f / sc0, is3 = 1.f / sc3;
         const unsigned ba0 = lds0 + BOFF + (unsigned)(tid & (2 * D - 1)) * 4u, ba3 = lds0 + BOFF + (unsigned)(2 * D + (tid & (D - 1))) * 4u;
@@ -250,27 +206,35 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     auto lds_read = [&](f16x8& dst, unsigned addr, int imm) { asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(imm)); };
     // this wave's fragment (block b, part) of the current weight stage: (b * 2 + part) KiB behind the base of its hidden half
     // (part 0 = hi, 1 = lo; fc.0 stages: b = t * 4 + i, fc.3 stages: b = output block i)
-    unsigned wa = 0;
+    // Ring addressing.  A stage whose ring slot is known at compile time reads through a loop-invariant base register plus an immediate:
+    // weights waA (slots 0 and 1) / waB (slot 2: the DS offset field has 16 bits), tokens xb + slot * XSTAGE.  The stages of the run-time
+    // fc.0 loop, and the first stage of a pass, read through wa / xa, which the hand-over in front of them sets ("run-time form").
+    unsigned waA = lds0 + (unsigned)(ha * 16384) + lane16, waB = waA + 2u * WSTAGE;
+    asm volatile("" : "+v"(waA), "+v"(waB));
+    unsigned wa = waA;
     const int swz = (l31 >> 1) & 7;
-    unsigned xk[2][2], xa[2][2];
+    unsigned xb[2][2], xa[2][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int hl = 0; hl < 2; ++hl)
-            xk[t][hl] = (unsigned)((tb * 32 + l31) * 128) + ((unsigned)(((2 * t + hi) ^ swz) * 16) ^ (hl ? 64u : 0u));
-    auto set_x = [&](int slot) {
-        const unsigned b = lds0 + XOFF + slot * XSTAGE;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) { xa[t][0] = b + xk[t][0]; xa[t][1] = b + xk[t][1]; }
+        for (int hl = 0; hl < 2; ++hl) {
+            xb[t][hl] = lds0 + XOFF + (unsigned)((tb * 32 + l31) * 128) + ((unsigned)(((2 * t + hi) ^ swz) * 16) ^ (hl ? 64u : 0u));
+            asm volatile("" : "+v"(xb[t][hl]));
+            xa[t][hl] = xb[t][hl];
+        }
+    // token fragments of k-step t from ring slot SLOT (compile time; < 0: run-time form)
+    auto read_xs = [&](auto SLOT, int t) {
+        constexpr int sl = decltype(SLOT)::value;
+        if constexpr (sl >= 0) { lds_read(xh[t], xb[t][0], sl * XSTAGE); lds_read(xl[t], xb[t][1], sl * XSTAGE); }
+        else { lds_read(xh[t], xa[t][0], 0); lds_read(xl[t], xa[t][1], 0); }
     };
-    auto read_x = [&](int t) { lds_read(xh[t], xa[t][0], 0); lds_read(xl[t], xa[t][1], 0); };
-    auto set_w = [&](int slot) { wa = lds0 + slot * WSTAGE + ha * 16384 + lane16; };
     // LDS returns in order: "all but the N newest reads have landed".  The "+v" operand ties the wait to the register it releases.
     auto wait1 = [&](int newer, f16x8& r) {
         if (newer == 0) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(r));
         else if (newer == 1) asm volatile("s_waitcnt lgkmcnt(1)" : "+v"(r));
         else if (newer == 2) asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(r));
         else if (newer == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r));
+        else if (newer == 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(r));
         else asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(r));
     };
     auto tie2 = [&](f16x8& a, f16x8& b) { asm volatile("" : "+v"(a), "+v"(b)); };
@@ -307,8 +271,12 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
         else init_acc2(acc3[2], acc3[3], 2 * D + 64);
     }
 
-    int s = 0, wslot = 0;           // weight stage being consumed and its ring slot
-    int xs = 0, xslot = 0;          // token stage being consumed (fc.0 stages only) and its ring slot
+    // (pinned, here and after the fc.0 initialisation of a pass: each accumulator is its own 16-register value from here on.  Without the pins
+    //  the register allocator keeps the pairs init_acc2 fills as 32-register values and spills accumulators at 128-d)
+#pragma unroll
+    for (int i = 0; i < NOB; ++i) asm volatile("" : "+v"(acc3[i]));
+    [[maybe_unused]] int s = 0;     // stage counter (trace builds)
+    int wslot = 0, xslot = 0;       // ring slots of the weight / token stage being consumed, kept where they are run-time values: the fc.0 loop
     auto next3 = [](int v) { return v == 2 ? 0 : v + 1; };
     auto prev3 = [](int v) { return v == 0 ? 2 : v - 1; };
 
@@ -317,8 +285,9 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     //      and waited for individually in front of the first MFMA that needs it (LDS returns in order).  LDS-DMA pieces, the token
     //      fragments of the second k-step and the (hi, lo) conversion of the next hidden fragments sit behind MFMAs 2 and 3, where no
     //      fragment read is issued.  The hand-over to the next stage (DMA wait + barrier) sits between MFMA 3 and 4 of the last
-    //      group, when all of this wave's reads of the stage have been waited for; the next stage's first fragments follow it. ----
-    auto hand_over = [&](bool next_exists, bool next_is_fc0, int next_xslot, int issued) {
+    //      group, when all of this wave's reads of the stage have been waited for; the next stage's first fragments follow it.
+    //      w_rt / x_rt: the next stage reads its weights / tokens in the run-time form, from ring slots nwslot / nxslot. ----
+    auto hand_over = [&](bool next_exists, bool w_rt, bool x_rt, int nwslot, int nxslot, int issued) {
         OG_MT(0, s);
         // everything issued before this stage has landed (only this stage's own pieces may still fly)
         if (issued == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -328,8 +297,12 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
         if (next_exists) {
             __builtin_amdgcn_s_barrier();
             OG_MT(2, s);
-            set_w(next3(wslot));
-            if (next_is_fc0) set_x(next_xslot);
+            if (w_rt) wa = waA + (unsigned)(nwslot * WSTAGE);
+            if (x_rt) {
+                const unsigned o = (unsigned)(nxslot * XSTAGE);
+#pragma unroll
+                for (int t = 0; t < 2; ++t) { xa[t][0] = xb[t][0] + o; xa[t][1] = xb[t][1] + o; }
+            }
         }
     };
 #define OG_SB() __builtin_amdgcn_sched_barrier(0)
@@ -349,7 +322,9 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
 #define OG_MM(acc_, a_, b_) acc_ = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_, b_, acc_, 0, 0, 0)
 #endif
     // fragment k of group G: k = 0: lo of block 2G, 1: lo of block 2G+1, 2: hi of block 2G, 3: hi of block 2G+1
-#define OG_RD(G, K) lds_read((K) < 2 ? wl[(K) & 1] : wh[(K) & 1], wa, ((2 * (G) + ((K) & 1)) * 2 + ((K) < 2 ? 1 : 0)) * 1024)
+    // (cur_wa + cur_wim: base register + immediate of the stage's weight ring slot; nxt_wa + nxt_wim: the next stage's, valid behind the hand-over)
+#define OG_RD(G, K) lds_read((K) < 2 ? wl[(K) & 1] : wh[(K) & 1], cur_wa, cur_wim + ((2 * (G) + ((K) & 1)) * 2 + ((K) < 2 ? 1 : 0)) * 1024)
+#define OG_RDN(K) lds_read((K) < 2 ? wl[(K) & 1] : wh[(K) & 1], nxt_wa, nxt_wim + (((K) & 1) * 2 + ((K) < 2 ? 1 : 0)) * 1024)
     // A0 / A1: the two accumulators; BH / BL: the B fragments; C0..C3: lgkmcnt in front of MFMAs 0..3; SLOT(k): extra work behind MFMA k
 #define OG_GROUP(A0, A1, BH, BL, G, C0, C1, C2, C3, SLOT)                                                     \
     {                                                                                                        \
@@ -369,10 +344,10 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
         wait1(0, wh[1]); OG_SB(); OG_MM(A1, wh[1], BL); OG_SB(); SLOT(3); OG_SB();                            \
         HANDOVER; OG_SB();             /* all my LDS reads of this stage have been waited for */              \
         OG_MM(A0, wh[0], BH); OG_SB();                                                                       \
-        if (NEXT_FC0) read_x(0);                                                                             \
-        if (NEXT_EXISTS) { OG_RD(0, 0); OG_RD(0, 1); OG_RD(0, 2); }                                           \
+        if (NEXT_FC0) read_x_next();                                                                         \
+        if (NEXT_EXISTS) { OG_RDN(0); OG_RDN(1); OG_RDN(2); }                                                 \
         OG_SB();                                                                                             \
-        OG_MM(A1, wh[1], BH); OG_SB(); if (NEXT_EXISTS) OG_RD(0, 3); OG_SB();                                 \
+        OG_MM(A1, wh[1], BH); OG_SB(); if (NEXT_EXISTS) OG_RDN(3); OG_SB();                                   \
     }
 
     // ---- the residual enters through the matrix pipe: x_new = x + W3' h  =>  acc3[i] += (S3 I) · x[channel block i], and the (hi, lo)
@@ -383,72 +358,92 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     //      the same extra work for all eight waves, so nobody arrives late at the stage barrier.  [Round 3, first version: residual rows fetched in the epilogue, turned into the accumulator layout through the LDS
     //      slabs and added with mixed-precision FMAs -- 8 global loads, 48 LDS operations and 32 VALU per wave of an epilogue that is
     //      bound by its LDS operations.]
-    const _Float16 s3h = (_Float16)(1.f / sc3);               // power of two >= 2^-14 (og_weight_prescale): exact in binary16
-    auto ident = [&](int t) {                                 // built where it is used (4 stages per tile): no registers held across the loop
-        int row = l31 - 8 * hi;
-        asm volatile("" : "+v"(row));                         // opaque: re-computed at every use, not hoisted out of the loop and spilled
-        f16x8 f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = (row == 16 * t + e) ? s3h : (_Float16)0.f;
-        return f;
-    };
+    //      The identity fragment is read from LDS (`ida`) once per such stage, behind MFMA 2 of the first group, by both waves of a token
+    //      block; an extra read only makes the counted waits of the groups stricter.  At its first use the reads newer than it are the
+    //      token fragments of k-step 1 and two weight fragments (t = 0: lgkmcnt(4)); at t = 1 the groups in between have waited past it.
 // RB_ >= 0 (compile time): this stage is k-group RB_ of the last quarter -- the wave that finishes output block RB_ adds its residual
-#define OG_RESID(RB_, T_, XF_)                                                                               \
+#define OG_RESID(RB_, T_, XF_, FIRST_)                                                                       \
     if constexpr ((RB_) >= 0) {                                                                              \
-        if (ha == (T_)) { const f16x8 idt_ = ident(T_); OG_MM(acc3[(RB_) < 0 ? 0 : (RB_)], idt_, XF_); OG_SB(); }   \
+        if (ha == (T_)) { if (FIRST_) wait1(4, idt); OG_SB(); OG_MM(acc3[(RB_) < 0 ? 0 : (RB_)], idt, XF_); OG_SB(); }   \
     }
 
-    set_w(0); set_x(0);
-    read_x(0);
-    OG_RD(0, 0); OG_RD(0, 1); OG_RD(0, 2); OG_RD(0, 3);
+    read_xs(std::integral_constant<int, -1>{}, 0);        // W(0), X(0): slot 0, run-time form (wa = waA, xa = xb)
+    {
+        const unsigned cur_wa = wa;
+        constexpr int cur_wim = 0;
+        OG_RD(0, 0); OG_RD(0, 1); OG_RD(0, 2); OG_RD(0, 3);
+    }
 
+    // A pass is G0 fc.0 stages + NJT fc.3 stages; the weight ring turns with every stage, the token ring with every fc.0 stage.  With more
+    // than one pass a pass is a multiple of three stages, so a pass starts on weight slot 0; its token slot depends on the pass.  The
+    // stages that are unrolled know their slots; only the last stages of the kernel ask whether what they would fetch exists:
+    //   fc.0 k-groups G0 - 2, G0 - 1 (token k-groups 0, 1 of the next pass), the last two fc.3 stages (weights), the last (hand-over).
+    // The fc.0 stage loop in front of them issues and reads unconditionally.
+    constexpr int LP = NPASS - 1;
 #pragma unroll 1
     for (int pass = 0; pass < NPASS; ++pass) {
         init_acc2(acc0[0], acc0[1], (HB2 * ha + 4 * pass) * 32);
         init_acc2(acc0[2], acc0[3], (HB2 * ha + 4 * pass + 2) * 32);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(acc0[i]));
 
         // ================= fc.0: acc0[i] += W0'[hidden block 8 ha + 4 pass + i][k-group] · [x ; O][k-group], 16 stages =================
-        auto fc0_stage = [&](int kg, auto RB) {
-            constexpr int rb = decltype(RB)::value;                     // >= 0: the residual of output block rb rides in this stage
-            const bool ix = xs + 2 < XSTAGES;                           // X(xs+2) exists (W(s+2) always does during fc.0)
-            const int wslot2 = prev3(wslot), xslot2 = prev3(xslot);     // slots of W(s+2), X(xs+2): (s + 2) % 3 = (s - 1) % 3
-            const bool next_x = kg + 1 < G0;                            // the next stage is an fc.0 stage (reads token fragments)
-#if OG_MLP_DMA_SPREAD
-#define OG_SLOT_G0(k) { if ((k) == 2) issue_w1(s + 2, wslot2, std::integral_constant<int, 0>{}); if ((k) == 3) { read_x(1); issue_w1(s + 2, wslot2, std::integral_constant<int, 1>{}); } }
-#define OG_SLOT_G1(k) { if ((k) == 2) issue_w1(s + 2, wslot2, std::integral_constant<int, 2>{}); if ((k) == 3) issue_w1(s + 2, wslot2, std::integral_constant<int, 3>{}); }
-#define OG_SLOT_G2(k) { if (ix) { if ((k) == 2) issue_x1(xs + 2, xslot2, std::integral_constant<int, 0>{}); if ((k) == 3) issue_x1(xs + 2, xslot2, std::integral_constant<int, 1>{}); } }
-#else
-#define OG_SLOT_G0(k) { if ((k) == 2 && !(OG_MLP_ABL & 8)) issue_w4(s + 2, wslot2); if ((k) == 3) read_x(1); }   /* the weight pieces; the second k-step's token fragments */
-#define OG_SLOT_G1(k) { if ((k) == 2 && ix && !(OG_MLP_ABL & (8 | 32))) issue_x2(xs + 2, xslot2); }                  /* the token pieces */
-#define OG_SLOT_G2(k) {}
-#endif
+        auto fc0_stage = [&](auto ST) {
+            using T = decltype(ST);
+            constexpr int rb = T::rb;
+            constexpr int cur_wim = og_ring_wim(T::cw), nxt_wim = og_ring_wim(T::nw);
+            const unsigned cur_wa = T::cw < 0 ? wa : T::cw == 2 ? waB : waA;
+            unsigned nxt_wa = cur_wa;
+            // W(s + 2), X(xs + 2) go to the slots of stages s - 1, xs - 1
+            const int wslot2 = T::cw < 0 ? prev3(wslot) : (T::cw + 2) % 3, xslot2 = T::cx < 0 ? prev3(xslot) : (T::cx + 2) % 3;
+            const bool ix = T::ix < 0 ? pass + 1 < NPASS : T::ix != 0;
+            constexpr bool next_x = T::nx != -2;
+            [[maybe_unused]] f16x8 idt;
+            auto read_x_next = [&]() { read_xs(std::integral_constant<int, T::nx>{}, 0); };
+            auto ho = [&]() {
+                hand_over(true, T::nw < 0, T::nx == -1, T::cw < 0 ? next3(wslot) : (T::cw + 1) % 3, T::cx < 0 ? next3(xslot) : (T::cx + 1) % 3, ix ? 6 : 4);
+                nxt_wa = T::nw < 0 ? wa : T::nw == 2 ? waB : waA;
+            };
+            // behind MFMA 2 of group 0: the identity fragment (residual stages), the weight pieces; behind MFMA 3: the second k-step's token fragments
+#define OG_SLOT_G0(k) { if ((k) == 2) { if constexpr (rb >= 0) lds_read(idt, ida, 0); if (!(OG_MLP_ABL & 8)) issue_w4(wslot2); } if ((k) == 3) read_xs(std::integral_constant<int, T::cx>{}, 1); }
+#define OG_SLOT_G1(k) { if ((k) == 2 && ix && !(OG_MLP_ABL & (8 | 32))) { if constexpr (T::xr != 0) xsrc = baseX; issue_x2(xslot2); } }      /* the token pieces */
 #define OG_SLOT_NONE(k) {}
             tie2(xh[0], xl[0]);
             OG_GROUP(acc0[0], acc0[1], xh[0], xl[0], 0, 3, 3, 3, 2, OG_SLOT_G0)
-            OG_RESID(rb, 0, xh[0])
+            OG_RESID(rb, 0, xh[0], true)
             OG_GROUP(acc0[2], acc0[3], xh[0], xl[0], 1, 5, 5, 3, 2, OG_SLOT_G1)
-            OG_RESID(rb, 0, xl[0])
+            OG_RESID(rb, 0, xl[0], false)
             tie2(xh[1], xl[1]);
-            OG_GROUP(acc0[0], acc0[1], xh[1], xl[1], 2, 3, 3, 3, 2, OG_SLOT_G2)
-            OG_RESID(rb, 1, xh[1])
-            OG_RESID(rb, 1, xl[1])
-            OG_GROUP_LAST(acc0[2], acc0[3], xh[1], xl[1], OG_SLOT_NONE, hand_over(true, next_x, next3(xslot), ix ? 6 : 4), true, next_x)
-            ++s; wslot = next3(wslot);
-            ++xs; xslot = next3(xslot);
+            OG_GROUP(acc0[0], acc0[1], xh[1], xl[1], 2, 3, 3, 3, 2, OG_SLOT_NONE)
+            OG_RESID(rb, 1, xh[1], true)
+            OG_RESID(rb, 1, xl[1], false)
+            OG_GROUP_LAST(acc0[2], acc0[3], xh[1], xl[1], OG_SLOT_NONE, ho(), true, next_x)
+            ++s;
         };
-        using NoRes = std::integral_constant<int, -1>;
-        int kg0 = 0;
-        if (pass == NPASS - 1) {        // the x half of [x ; O] (k-groups 0..NOB-1) in the last pass: unrolled, every stage knows its output block
-            fc0_stage(0, std::integral_constant<int, 0>{}); fc0_stage(1, std::integral_constant<int, 1>{});
-            fc0_stage(2, std::integral_constant<int, 2>{}); fc0_stage(3, std::integral_constant<int, 3>{});
-            if constexpr (NOB == 8) {
-                fc0_stage(4, std::integral_constant<int, 4>{}); fc0_stage(5, std::integral_constant<int, 5>{});
-                fc0_stage(6, std::integral_constant<int, 6>{}); fc0_stage(7, std::integral_constant<int, 7>{});
-            }
-            kg0 = NOB;
+        wslot = 0;
+        int kg = 0;
+        if (pass == LP) {        // the x half of [x ; O] (k-groups 0..NOB-1) in the last pass: unrolled, every stage knows its output block and its slots
+            xslot = (LP * G0) % 3;
+            // (stage 0 is entered in the run-time form, as the first stage of every pass; the last one hands over to the loop)
+#define OG_RS(K) fc0_stage(OgFc0Stage<(K) == 0 ? -1 : (K) % 3, (K) == 0 ? -1 : (LP * G0 + (K)) % 3, (K) == NOB - 1 ? -1 : ((K) + 1) % 3, (K) == NOB - 1 ? -1 : (LP * G0 + (K) + 1) % 3, (K), 1, 0>{})
+            OG_RS(0); OG_RS(1); OG_RS(2);
+            if constexpr (NOB == 8) { OG_RS(3); OG_RS(4); OG_RS(5); OG_RS(6); }
+            OG_RS(NOB - 1);
+#undef OG_RS
+            wslot = NOB % 3; xslot = (LP * G0 + NOB) % 3;
+            kg = NOB;
         }
 #pragma unroll 1
-        for (int kg = kg0; kg < G0; ++kg) fc0_stage(kg, NoRes{});
+        for (; kg < G0 - 2; ++kg) {
+            fc0_stage(OgFc0Stage<-1, -1, -1, -1, -1, 1, 0>{});
+            wslot = next3(wslot); xslot = next3(xslot);
+        }
+        fc0_stage(OgFc0Stage<-1, -1, (G0 - 1) % 3, -1, -1, (NPASS > 1 ? -1 : 0), 1>{});        // k-group G0 - 2
+        xslot = next3(xslot);
+        fc0_stage(OgFc0Stage<(G0 - 1) % 3, -1, G0 % 3, -2, -1, (NPASS > 1 ? -1 : 0), 0>{});    // k-group G0 - 1
+        xslot = next3(xslot);                                                                  // = the token slot the next pass starts on
+#undef OG_SLOT_G0
+#undef OG_SLOT_G1
 
         // ================= fc.3: acc3[i] += W3'[block i][hidden block 8 ha + 4 pass + j] · relu(acc0[j] / 256), 8 stages (j, t) =================
         // hidden block j as B fragments: element e of k-step t is accumulator register 8t + e (og_pack_mlp_stream permutes W3' to match)
@@ -464,49 +459,50 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
                 og_split4(cv[0], cv[1], cv[2], cv[3], hh[buf][2 * h], hl[buf][2 * h], hh[buf][2 * h + 1], hl[buf][2 * h + 1]);
             }
         };
+        auto read_x_next = [&]() { read_xs(std::integral_constant<int, -1>{}, 0); };      // (the first stage of the next pass: run-time form)
+        const bool lastp = pass == LP;
 #pragma unroll
         for (int st = 0; st < 4; ++st) convert_step(acc0[0], 0, st, 0);
-        if constexpr (D == 256) {
-#pragma unroll
-            for (int jt = 0; jt < NJT; ++jt) {
-                const bool iw = s + 2 < STAGES;
-                const int wslot2 = prev3(wslot);
-                const bool next_exists = s + 1 < STAGES;
-                const bool next_x = jt + 1 == NJT && pass + 1 < NPASS;      // the next stage is the first fc.0 stage of the next quarter
-                const int hb = jt & 1;
+        // fc.3 stage j of the pass (compile time: all of them are unrolled).  Its weight slot is (G0 + j) % 3; the last one hands over to the
+        // next pass (run-time form: weight slot 0, token slot xslot) or to nobody.
+#define OG_FC3_STAGE_VARS(j_)                                                                                \
+        const bool iw = !((j_) >= NJT - 2 && lastp);                  /* W(s + 2) exists */                  \
+        const bool next_exists = !((j_) == NJT - 1 && lastp);                                                \
+        const bool next_x = (j_) == NJT - 1 && !lastp;                /* the next stage is the first fc.0 stage of the next pass */   \
+        constexpr int cw = (G0 + (j_)) % 3, wslot2 = (cw + 2) % 3, nw = (cw + 1) % 3;                        \
+        constexpr bool nw_rt = (j_) == NJT - 1;                                                              \
+        const unsigned cur_wa = cw == 2 ? waB : waA;                                                         \
+        constexpr int cur_wim = og_ring_wim(cw), nxt_wim = nw_rt ? 0 : og_ring_wim(nw);                      \
+        unsigned nxt_wa = cur_wa;                                                                            \
+        auto ho = [&]() {                                                     \
+            hand_over(next_exists, nw_rt, next_x, 0, xslot, iw ? 4 : 0);                                     \
+            if constexpr (nw_rt) nxt_wa = wa;                                                                \
+            else nxt_wa = nw == 2 ? waB : waA;                                                               \
+        };
+        auto fc3_stage = [&](auto J) {
+            constexpr int j = decltype(J)::value;
+            OG_FC3_STAGE_VARS(j)
+            if constexpr (D == 256) {
+                // stage j = (hidden block j / 2, k-step j & 1) over the 8 output blocks
+                constexpr int hb = j & 1;
                 const f16x8 bh = __builtin_bit_cast(f16x8, og_u32x4{hh[hb][0], hh[hb][1], hh[hb][2], hh[hb][3]});
                 const f16x8 bl = __builtin_bit_cast(f16x8, og_u32x4{hl[hb][0], hl[hb][1], hl[hb][2], hl[hb][3]});
-                constexpr int NXT = 0;
-                (void)NXT;
-                // the next stage's B fragments: hidden block (jt + 1) / 2, k-step (jt + 1) & 1
-                auto conv = [&](int step) { if (jt + 1 < NJT) convert_step(acc0[(jt + 1 < NJT ? jt + 1 : jt) >> 1], (jt + 1) & 1, step, hb ^ 1); };
-#if OG_MLP_DMA_SPREAD
-#define OG_SLOT_P0(k) { if (iw) { if ((k) == 2) issue_w1(s + 2, wslot2, std::integral_constant<int, 0>{}); else issue_w1(s + 2, wslot2, std::integral_constant<int, 1>{}); } }
-#define OG_SLOT_P1(k) { if (iw) { if ((k) == 2) issue_w1(s + 2, wslot2, std::integral_constant<int, 2>{}); else issue_w1(s + 2, wslot2, std::integral_constant<int, 3>{}); } }
-#else
-#define OG_SLOT_P0(k) { if ((k) == 2 && iw && !(OG_MLP_ABL & 8)) issue_w4(s + 2, wslot2); }
-#define OG_SLOT_P1(k) {}
-#endif
+                // the next stage's B fragments: hidden block (j + 1) / 2, k-step (j + 1) & 1
+                auto conv = [&](int step) { if constexpr (j + 1 < NJT) convert_step(acc0[(j + 1 < NJT ? j + 1 : j) >> 1], (j + 1) & 1, step, hb ^ 1); };
+#define OG_SLOT_P0(k) { if ((k) == 2 && iw && !(OG_MLP_ABL & 8)) issue_w4(wslot2); }
 #define OG_SLOT_C2(k) conv((k) - 2)
 #define OG_SLOT_C3(k) conv((k))
                 OG_GROUP(acc3[0], acc3[1], bh, bl, 0, 3, 3, 3, 2, OG_SLOT_P0)
-                OG_GROUP(acc3[2], acc3[3], bh, bl, 1, 3, 3, 3, 2, OG_SLOT_P1)
-                OG_GROUP(acc3[4], acc3[5], bh, bl, 2, 3, 3, 3, 2, OG_SLOT_C2)
-                OG_GROUP_LAST(acc3[6], acc3[7], bh, bl, OG_SLOT_C3, hand_over(next_exists, next_x, xslot, iw ? 4 : 0), next_exists, next_x)
-                ++s; wslot = next3(wslot);
-            }
-        } else {
-            // 128-d: stage j = hidden block j with BOTH k-steps over the 4 output blocks: groups 0, 1 take k-step 0 (B fragments in buffer 0), groups
-            // 2, 3 k-step 1 (buffer 1).  Conversions ride behind the MFMAs as above: k-step 1 of block j (into buffer 1) during groups 0, 1,
-            // k-step 0 of block j + 1 (into buffer 0, free once group 1 has issued) during groups 2, 3.
-#pragma unroll
-            for (int j = 0; j < NJT; ++j) {
-                const bool iw = s + 2 < STAGES;
-                const int wslot2 = prev3(wslot);
-                const bool next_exists = s + 1 < STAGES;
+                OG_GROUP(acc3[2], acc3[3], bh, bl, 1, 3, 3, 3, 2, OG_SLOT_NONE)
+                OG_GROUP(acc3[NOB == 8 ? 4 : 0], acc3[NOB == 8 ? 5 : 1], bh, bl, 2, 3, 3, 3, 2, OG_SLOT_C2)
+                OG_GROUP_LAST(acc3[NOB == 8 ? 6 : 2], acc3[NOB == 8 ? 7 : 3], bh, bl, OG_SLOT_C3, ho(), next_exists, next_x)
+            } else {
+                // 128-d: stage j = hidden block j with BOTH k-steps over the 4 output blocks: groups 0, 1 take k-step 0 (B fragments in buffer 0), groups
+                // 2, 3 k-step 1 (buffer 1).  Conversions ride behind the MFMAs as above: k-step 1 of block j (into buffer 1) during groups 0, 1,
+                // k-step 0 of block j + 1 (into buffer 0, free once group 1 has issued) during groups 2, 3.
                 auto conv1 = [&](int step) { convert_step(acc0[j], 1, step, 1); };
-                auto conv0n = [&](int step) { if (j + 1 < NJT) convert_step(acc0[j + 1 < NJT ? j + 1 : j], 0, step, 0); };
-#define OG_SLOT_Q0(k) { if ((k) == 2 && iw && !(OG_MLP_ABL & 8)) issue_w4(s + 2, wslot2); conv1((k) - 2); }
+                auto conv0n = [&](int step) { if constexpr (j + 1 < NJT) convert_step(acc0[j + 1 < NJT ? j + 1 : j], 0, step, 0); };
+#define OG_SLOT_Q0(k) { if ((k) == 2 && iw && !(OG_MLP_ABL & 8)) issue_w4(wslot2); conv1((k) - 2); }
 #define OG_SLOT_Q1(k) conv1((k))
 #define OG_SLOT_Q2(k) conv0n((k) - 2)
 #define OG_SLOT_Q3(k) conv0n((k))
@@ -520,10 +516,17 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
                     const f16x8 bh = __builtin_bit_cast(f16x8, og_u32x4{hh[1][0], hh[1][1], hh[1][2], hh[1][3]});
                     const f16x8 bl = __builtin_bit_cast(f16x8, og_u32x4{hl[1][0], hl[1][1], hl[1][2], hl[1][3]});
                     OG_GROUP(acc3[0], acc3[1], bh, bl, 2, 3, 3, 3, 2, OG_SLOT_Q2)
-                    OG_GROUP_LAST(acc3[2], acc3[3], bh, bl, OG_SLOT_Q3, hand_over(next_exists, false, xslot, iw ? 4 : 0), next_exists, false)
+                    OG_GROUP_LAST(acc3[2], acc3[3], bh, bl, OG_SLOT_Q3, ho(), next_exists, false)
                 }
-                ++s; wslot = next3(wslot);
             }
+            ++s;
+        };
+#undef OG_FC3_STAGE_VARS
+        fc3_stage(std::integral_constant<int, 0>{}); fc3_stage(std::integral_constant<int, 1>{});
+        fc3_stage(std::integral_constant<int, 2>{}); fc3_stage(std::integral_constant<int, 3>{});
+        if constexpr (NJT == 8) {
+            fc3_stage(std::integral_constant<int, 4>{}); fc3_stage(std::integral_constant<int, 5>{});
+            fc3_stage(std::integral_constant<int, 6>{}); fc3_stage(std::integral_constant<int, 7>{});
         }
     }
 #undef OG_RESID
@@ -532,92 +535,111 @@ __global__ __launch_bounds__(512) void mlp_fused_kernel(MlpFusedArgs g) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     OG_MT(3, 1);
     const int tok0 = t0 + tb * 32;
-    char* const rows = reinterpret_cast<char*>(g.XO);
-    int64_t rowb[4];                                          // byte offset of this lane's row per store instruction
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        int r = tok0 + it * 8 + (lane >> 3);
-        if (r > g.M - 1) r = g.M - 1;
-        rowb[it] = (int64_t)r * g.ld * 2 + (lane & 7) * 16 + NOBH * ha * 128;
-    }
+    const bool full = t0 + MT <= g.M;                        // block-uniform
+    const int64_t ldb = g.ld * 2;
     __syncthreads();          // every wave is past its last fragment reads, no DMA in flight: the rings are free
 
-    // ================= the two waves of a token block exchange half of their partial sums =================
-    // Wave (tb, a) finishes output blocks NOBH a .. NOBH a + NOBH - 1 and hands its partial sums of the other NOBH to its partner: 16 KiB per wave at 256-d,
-    // [block][register group][lane] x 16 B (conflict-free), region `wave`; afterwards the region a wave has READ belongs to it alone
-    // (epilogue slabs).
-    f32x16 accf[NOBH];
-    {
-        char* const mine = smem + wave * 16384;
-        char* const theirs = smem + (wave ^ 1) * 16384;
-        const bool lowhalf = ha == 0;                          // wave-uniform; element-wise selects keep the accumulators in registers
+    // Everything below runs under ONE wave-uniform branch on the hidden half (two straight-line bodies): which accumulators a wave hands
+    // over and which it keeps is then a compile-time choice, and the accumulators stay in registers without element-wise selects.
+    auto tail = [&](auto HA) {
+        constexpr int h = decltype(HA)::value;
+        // ================= the two waves of a token block exchange half of their partial sums =================
+        // Wave (tb, a) finishes output blocks NOBH a .. NOBH a + NOBH - 1 and hands its partial sums of the other NOBH to its partner: 16 KiB per wave at 256-d,
+        // [block][register group][lane] x 16 B (conflict-free), region `wave`; afterwards the region a wave has READ belongs to it alone
+        // (epilogue slabs).
+        f32x16 accf[NOBH];
+        {
+            char* const mine = smem + wave * 16384;
+            char* const theirs = smem + (wave ^ 1) * 16384;
 #pragma unroll
-        for (int i = 0; i < NOBH; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 v;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = lowhalf ? acc3[NOBH + i][4 * q + e] : acc3[i][4 * q + e];
-                *reinterpret_cast<f32x4*>(mine + ((i * 4 + q) * 64 + lane) * 16) = v;
-            }
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NOBH; ++i) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(theirs + ((i * 4 + q) * 64 + lane) * 16);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) accf[i][4 * q + e] = (lowhalf ? acc3[i][4 * q + e] : acc3[NOBH + i][4 * q + e]) + v[e];
-            }
-        }
-    }
-
-    // ================= epilogue: x <- acc / S3 (bias and residual inside), written back as hl32 rows =================
-    // A lane owns ONE token and 4 consecutive channels per register group.  Result rows go out as whole 128-byte lines (one channel
-    // block of one token: 64 B hi | 64 B lo), 8 rows per instruction, through two per-wave LDS slabs (as gemm_f16x3_epilogue_fast),
-    // channel blocks in pairs.
-    {
-#pragma clang fp contract(off)
-        constexpr int ROWB = 128 + 16;
-        char* const slab2 = smem + (wave ^ 1) * 16384;
-        const unsigned rd_off = (unsigned)((lane >> 3) * ROWB + (lane & 7) * 16);
-        const bool full = t0 + MT <= g.M;                    // block-uniform
-#pragma unroll
-        for (int ip = 0; ip < NOBH / 2; ++ip) {
-            f32x16 a[2];
-            a[0] = accf[2 * ip]; a[1] = accf[2 * ip + 1];
-            // v = acc / S3 (bias and residual are inside the accumulator); pinned: og_split4 must see ONE rounded product
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                a[i] = a[i] * sc3;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(a[i][r]));
-            }
-            // registers -> slabs: slab i = [32 tok][hi 64 B | lo 64 B] of channel block cb0 + 2 ip + i
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < NOBH; ++i)
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    unsigned ha2, la, hb2, lb;
-                    og_split4(a[i][4 * q], a[i][4 * q + 1], a[i][4 * q + 2], a[i][4 * q + 3], ha2, la, hb2, lb);
-                    char* d = slab2 + i * EPI_SLAB + l31 * ROWB + (8 * q + 4 * hi) * 2;
-                    *reinterpret_cast<uint2*>(d) = make_uint2(ha2, hb2);
-                    *reinterpret_cast<uint2*>(d + 64) = make_uint2(la, lb);
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = acc3[NOBH * (1 - h) + i][4 * q + e];
+                    *reinterpret_cast<f32x4*>(mine + ((i * 4 + q) * 64 + lane) * 16) = v;
                 }
-            // slabs -> whole 128-byte lines
+            __syncthreads();
 #pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                f16x8 tt[4];
+            for (int i = 0; i < NOBH; ++i) {
 #pragma unroll
-                for (int it = 0; it < 4; ++it) tt[it] = *reinterpret_cast<const f16x8*>(slab2 + i * EPI_SLAB + it * 8 * ROWB + rd_off);
+                for (int q = 0; q < 4; ++q) {
+                    const f32x4 v = *reinterpret_cast<const f32x4*>(theirs + ((i * 4 + q) * 64 + lane) * 16);
 #pragma unroll
-                for (int it = 0; it < 4; ++it) {
-                    if (OG_MLP_ABL & 1) continue;
-                    if (full || tok0 + it * 8 + (lane >> 3) < g.M) *reinterpret_cast<f16x8*>(rows + rowb[it] + (2 * ip + i) * 128) = tt[it];
+                    for (int e = 0; e < 4; ++e) accf[i][4 * q + e] = acc3[NOBH * h + i][4 * q + e] + v[e];
                 }
             }
         }
-    }
+
+        // ================= epilogue: x <- acc / S3 (bias and residual inside), written back as hl32 rows =================
+        // A lane owns ONE token and 4 consecutive channels per register group.  Result rows go out as whole 128-byte lines (one channel
+        // block of one token: 64 B hi | 64 B lo), 8 rows per instruction, through two per-wave LDS slabs (as gemm_f16x3_epilogue_fast),
+        // channel blocks in pairs.  Store addresses of a whole tile: one scalar base per group of 8 rows (the wave's first row and channel
+        // block, + 8 it rows) + ONE lane offset + the channel block as an immediate; only a partial last tile clamps and predicates rows.
+        {
+#pragma clang fp contract(off)
+            constexpr int ROWB = 128 + 16;
+            char* const slab2 = smem + (wave ^ 1) * 16384;
+            const unsigned rd_off = (unsigned)((lane >> 3) * ROWB + (lane & 7) * 16);
+            char* const wbase = reinterpret_cast<char*>(g.XO) + (int64_t)tok0 * ldb + NOBH * h * 128;      // uniform
+            unsigned voff = (unsigned)((lane >> 3) * (int)ldb + (lane & 7) * 16);
+            asm volatile("" : "+v"(voff));
+            auto store_lines = [&](const f16x8 (&tt)[4], auto CB) {       // the four 8-row groups of channel block CB (of this wave's NOBH)
+                constexpr int imm = decltype(CB)::value * 128;
+                if (OG_MLP_ABL & 1) return;
+                if (full) {
+#pragma unroll
+                    for (int it = 0; it < 4; ++it) {
+                        const char* const sb = wbase + (int64_t)(it * 8) * ldb;
+                        asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3" :: "v"(voff), "v"(tt[it]), "s"(sb), "n"(imm) : "memory");
+                    }
+                } else {
+#pragma unroll
+                    for (int it = 0; it < 4; ++it) {
+                        const int r = tok0 + it * 8 + (lane >> 3);
+                        if (r < g.M) *reinterpret_cast<f16x8*>(wbase + (int64_t)(r - tok0) * ldb + (lane & 7) * 16 + imm) = tt[it];
+                    }
+                }
+            };
+#pragma unroll
+            for (int ip = 0; ip < NOBH / 2; ++ip) {
+                f32x16 a[2];
+                a[0] = accf[2 * ip]; a[1] = accf[2 * ip + 1];
+                // v = acc / S3 (bias and residual are inside the accumulator); pinned: og_split4 must see ONE rounded product
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    a[i] = a[i] * sc3;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(a[i][r]));
+                }
+                // registers -> slabs: slab i = [32 tok][hi 64 B | lo 64 B] of channel block cb0 + 2 ip + i
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        unsigned ha2, la, hb2, lb;
+                        og_split4(a[i][4 * q], a[i][4 * q + 1], a[i][4 * q + 2], a[i][4 * q + 3], ha2, la, hb2, lb);
+                        char* d = slab2 + i * EPI_SLAB + l31 * ROWB + (8 * q + 4 * hi) * 2;
+                        *reinterpret_cast<uint2*>(d) = make_uint2(ha2, hb2);
+                        *reinterpret_cast<uint2*>(d + 64) = make_uint2(la, lb);
+                    }
+                // slabs -> whole 128-byte lines
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    f16x8 tt[4];
+#pragma unroll
+                    for (int it = 0; it < 4; ++it) tt[it] = *reinterpret_cast<const f16x8*>(slab2 + i * EPI_SLAB + it * 8 * ROWB + rd_off);
+                    if (ip == 0 && i == 0) store_lines(tt, std::integral_constant<int, 0>{});
+                    else if (ip == 0) store_lines(tt, std::integral_constant<int, 1>{});
+                    else if (i == 0) store_lines(tt, std::integral_constant<int, 2>{});
+                    else store_lines(tt, std::integral_constant<int, 3>{});
+                }
+            }
+        }
+    };
+    if (ha == 0) tail(std::integral_constant<int, 0>{});
+    else tail(std::integral_constant<int, 1>{});
 #if OG_MLP_TRACE
     OG_MT(3, 2);                                   // all stores issued
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -770,7 +792,9 @@ __global__ __launch_bounds__(512) void proj_stream_kernel(ProjStreamArgs g) {
         else if (newer == 3) asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(r));
         else asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(r));
     };
-    auto read_x = [&](int) {};                             // (the stage groups' hook for token fragments: they live in registers here)
+    auto read_x_next = [&] {};                             // (the stage groups' hook for token fragments: they live in registers here)
+    unsigned &cur_wa = wa, &nxt_wa = wa;                   // (... and for the weight ring slot: always `wa`, which the hand-over moves)
+    constexpr int cur_wim = 0, nxt_wim = 0;
     auto init_acc2 = [&](f32x16& a0, f32x16& a1, int off) {          // as in mlp_fused_kernel: own asm reads, own full wait
         const unsigned ad = lds0 + PBOFF + (unsigned)(off + 4 * hi) * 4u;
         f32x4 b[2][4];
@@ -904,6 +928,7 @@ __global__ __launch_bounds__(512) void proj_stream_kernel(ProjStreamArgs g) {
 #undef OG_GROUP_LAST
 #undef OG_MM
 #undef OG_RD
+#undef OG_RDN
 
 
 // =================================================================================================================================

@@ -16,6 +16,8 @@
 //     the chip sees reads, matrix work and writes interleaved for the whole life of the launch.
 // Arithmetic: as big2 (accumulator = bias / scale; k-steps ascending; per k-step Wl xh, Wh xl, Wh xh; times scale; og_split4): the
 // planes are bit-identical to that kernel's.  No communication between workgroups.
+#include <type_traits>
+
 #include "og_common.h"
 #include "og_proj_deal.h"
 
@@ -59,22 +61,48 @@ __global__ __launch_bounds__(512) void proj_wstat_kernel(ProjWstatArgs g) {
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
     // ---- token blocks: wave w fetches k-group w (one 128-byte line per row) of the 32 rows, 8 rows per DMA piece; 16-byte chunk c of
-    //      row r lands at chunk c ^ ((r >> 1) & 7) (swizzle on the source address, matched by the fragment reads).  Rows past M are
-    //      clamped: computed, never stored ----
-    const char* const xbase = reinterpret_cast<const char*>(g.X) + wave * 128;
-    auto issue_block = [&](int n, int slot) {
-        const int row0 = (blk0 + n) * WS_BLK;
+    //      row r lands at chunk c ^ ((r >> 1) & 7) (swizzle on the source address, matched by the fragment reads).
+    //      Addressing (as the attention tile loop): a SCALAR block base + four loop-invariant 32-bit lane offsets, the four
+    //      pieces in ONE asm block with one M0 write.  The instruction offset h KiB moves the LDS AND the global address, so the lane
+    //      offset of piece h takes it back out and the base sits 3 KiB low to keep every lane offset non-negative.  The blocks of a run
+    //      are issued in order: the base advances by a scalar add of 32 rows per issue.  Rows past M are clamped (computed, never
+    //      stored): only the run's LAST block can hold such rows, it has its own offsets (xoffc: equal to xoff when that block is whole) ----
+    const int64_t ldb = g.ld * 2;
+    unsigned xoff[4], xoffc[4];
+    {
+        const int lastrt = g.M - 1 - (blk1 - 1) * WS_BLK;
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
             const int rt = h * 8 + (lane >> 3);
-            int row = row0 + rt;
-            row = row < g.M ? row : g.M - 1;
-            const char* src = xbase + (int64_t)row * g.ld * 2 + (((lane & 7) ^ ((rt >> 1) & 7)) << 4);
-            __builtin_amdgcn_global_load_lds((og_glb_void*)src, (og_lds_void*)(smem + slot * WS_SLOT + wave * 4096 + h * 1024), 16, 0, 0);
+            const unsigned ch = (unsigned)((((lane & 7) ^ ((rt >> 1) & 7)) << 4) + (3 - h) * 1024);
+            xoff[h] = (unsigned)(rt * (int)ldb) + ch;
+            xoffc[h] = (unsigned)((rt < lastrt ? rt : lastrt) * (int)ldb) + ch;
+            asm volatile("" : "+v"(xoff[h]), "+v"(xoffc[h]));
         }
+    }
+    const char* xsrc = reinterpret_cast<const char*>(g.X) + wave * 128 + (int64_t)blk0 * WS_BLK * ldb - 3072;      // the next block to issue; uniform
+    const int64_t xstep = WS_BLK * ldb;
+    const unsigned m0_wave = lds0 + (unsigned)(wave * 4096);
+    auto issue_pieces = [&](const unsigned (&o)[4], int slot) {
+        const unsigned m0v = m0_wave + (unsigned)(slot * WS_SLOT);
+        asm volatile("s_mov_b32 m0, %5\n\t"
+                     "s_nop 0\n\t"
+                     "global_load_lds_dwordx4 %0, %4\n\t"
+                     "global_load_lds_dwordx4 %1, %4 offset:1024\n\t"
+                     "global_load_lds_dwordx4 %2, %4 offset:2048\n\t"
+                     "global_load_lds_dwordx4 %3, %4 offset:3072"
+                     :: "v"(o[0]), "v"(o[1]), "v"(o[2]), "v"(o[3]), "s"(xsrc), "s"(m0v) : "memory");
+        xsrc += xstep;
     };
-    issue_block(0, 0);
-    if (cnt > 1) issue_block(1, 1);
+    // block n of the run (the blocks are issued in order: xsrc points at it).  STEADY: known not to be the run's last block
+    auto issue_block = [&](auto STEADY, int n, int slot) {
+        if (decltype(STEADY)::value || n + 1 < cnt) issue_pieces(xoff, slot);
+        else issue_pieces(xoffc, slot);
+    };
+    using Steady = std::integral_constant<bool, true>;
+    using Generic = std::integral_constant<bool, false>;
+    issue_block(Generic{}, 0, 0);
+    if (cnt > 1) issue_block(Generic{}, 1, 1);
 
     // ---- this wave's weights and bias ----
     const int col0 = slab * 256 + wave * 32;
@@ -137,7 +165,16 @@ __global__ __launch_bounds__(512) void proj_wstat_kernel(ProjWstatArgs g) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) ew[q] = slab0 + (unsigned)(l31 * 64 + ((q ^ ((l31 >> 2) & 3)) << 4) + hi * 8);
     const unsigned er = slab0 + (unsigned)((lane >> 2) * 64 + (((lane & 3) ^ ((lane >> 4) & 3)) << 4));
-    const unsigned soff = (unsigned)((lane >> 2) * (int)g.ldc * 2 + col0 * 2 + (lane & 3) * 16);      // store i of a plane: rows 16 i + (lane >> 2)
+    // Store addressing: two 64-bit plane bases per wave (SGPRs: the tile to store next; tiles are stored in order, the bases advance by a scalar
+    // add of 32 rows behind a tile's lo plane) + two loop-invariant lane offsets, rows (lane >> 2) and 16 + (lane >> 2) of the tile.
+    const int64_t ldcb = g.ldc * 2;
+    unsigned soff[2];
+    soff[0] = (unsigned)((lane >> 2) * (int)ldcb + col0 * 2 + (lane & 3) * 16);
+    soff[1] = soff[0] + (unsigned)(16 * (int)ldcb);
+    asm volatile("" : "+v"(soff[0]), "+v"(soff[1]));
+    char* sch = reinterpret_cast<char*>(g.Ch) + (int64_t)blk0 * WS_BLK * ldcb;
+    char* scl = reinterpret_cast<char*>(g.Cl) + (int64_t)blk0 * WS_BLK * ldcb;
+    const int64_t sstep = WS_BLK * ldcb;
     unsigned ph[4][2], pl[4][2];
     f16x8 tt[2];
     auto epi_split = [&](f32x16& a) {
@@ -163,16 +200,23 @@ __global__ __launch_bounds__(512) void proj_wstat_kernel(ProjWstatArgs g) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(tt[i]) : "v"(er), "i"(p * 2048 + i * 1024) : "memory");
     };
-    auto epi_store = [&](int n, int p, int newer) {
+    // FULL: a whole tile (every tile but the last of a run): no row predicate
+    auto epi_store = [&](auto FULL, int p, int newer) {
         if (newer >= 4) asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(tt[0]), "+v"(tt[1]) :: "memory");
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tt[0]), "+v"(tt[1]) :: "memory");
-        const int row0 = (blk0 + n) * WS_BLK;
-        const bool full = row0 + WS_BLK <= g.M;
+        char* const base = p ? scl : sch;
+        if constexpr (decltype(FULL)::value) {
+            if (!(OG_WSTAT_ABL & 1))
+                asm volatile("global_store_dwordx4 %0, %2, %4\n\t"
+                             "global_store_dwordx4 %1, %3, %4"
+                             :: "v"(soff[0]), "v"(soff[1]), "v"(tt[0]), "v"(tt[1]), "s"(base) : "memory");
+        } else {
+            const int left = g.M - (blk1 - 1) * WS_BLK - (lane >> 2);      // rows of the run's last tile from this lane's first row on
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            char* q = reinterpret_cast<char*>(p ? g.Cl : g.Ch) + (int64_t)(row0 + i * 16) * g.ldc * 2;
-            if (!(OG_WSTAT_ABL & 1) && (full || row0 + i * 16 + (lane >> 2) < g.M)) *reinterpret_cast<f16x8*>(q + soff) = tt[i];
+            for (int i = 0; i < 2; ++i)
+                if (!(OG_WSTAT_ABL & 1) && i * 16 < left) *reinterpret_cast<f16x8*>(base + soff[i]) = tt[i];
         }
+        if (p) { sch += sstep; scl += sstep; }
     };
 
     // everything this wave asked for so far has landed: block 0, block 1, weights, bias
@@ -181,18 +225,23 @@ __global__ __launch_bounds__(512) void proj_wstat_kernel(ProjWstatArgs g) {
     // Block n.  Vector-memory operations complete in issue order; at the top of block n >= 2 the operations younger than the pieces of
     // block n (issued at the top of block n - 2) are the 4 stores of tile n - 3, the 4 pieces of block n + 1 and the 4 stores of tile n - 2
     // (all of them full tiles: only the last tile of a run can be partial).
-    auto do_block = [&](f32x16& acc, f32x16& prev, int n, int slot) __attribute__((always_inline)) {
-        if (n >= 2) {
+    // STEADY (compile time): 3 <= n and n + 2 is not the run's last block -- the wait is vmcnt(12), the pieces of block n + 2 are issued
+    // unconditionally with the unclamped offsets, the tile of block n - 1 is written.  The first three and the last (up to four) blocks
+    // of a run take the generic form, which asks.
+    auto do_block = [&](auto STEADY, f32x16& acc, f32x16& prev, int n, int slot) __attribute__((always_inline)) {
+        constexpr bool steady = decltype(STEADY)::value;
+        if (steady) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
+        else if (n >= 2) {
             const bool nxt = n + 1 < cnt, old = n >= 3;
             if (nxt && old) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
             else if (nxt || old) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         }
         __builtin_amdgcn_s_barrier();       // every wave's pieces of block n are in LDS; every wave is past its reads of block n - 1
-        if (n + 2 < cnt && !(OG_WSTAT_ABL & 8)) issue_block(n + 2, slot == 0 ? 2 : slot - 1);      // (n + 2) % 3: the slot of block n - 1
+        if ((steady || n + 2 < cnt) && !(OG_WSTAT_ABL & 8)) issue_block(STEADY, n + 2, slot == 0 ? 2 : slot - 1);      // (n + 2) % 3: the slot of block n - 1
         set_x(slot);
         read_x(0, 0);
-        const bool ep = n > 0 && !(OG_WSTAT_ABL & 16);
+        const bool ep = (steady || n > 0) && !(OG_WSTAT_ABL & 16);
 #pragma unroll
         for (int ks = 0; ks < 16; ++ks) {
             if (ks < 15 && !(OG_WSTAT_ABL & 4)) read_x(ks + 1, (ks + 1) & 1);
@@ -202,9 +251,9 @@ __global__ __launch_bounds__(512) void proj_wstat_kernel(ProjWstatArgs g) {
                 if (ks == 1) epi_split(prev);
                 if (ks == 3) epi_write();
                 if (ks == 5) epi_read(0);
-                if (ks == 7) epi_store(n - 1, 0, 4);
+                if (ks == 7) epi_store(std::true_type{}, 0, 4);
                 if (ks == 8) epi_read(1);
-                if (ks == 10) epi_store(n - 1, 1, 4);
+                if (ks == 10) epi_store(std::true_type{}, 1, 4);
             }
             wait_frag(ks & 1, ks < 15 ? 2 : 0);
             __builtin_amdgcn_sched_barrier(0);
@@ -219,29 +268,43 @@ __global__ __launch_bounds__(512) void proj_wstat_kernel(ProjWstatArgs g) {
             __builtin_amdgcn_sched_barrier(0);
         }
     };
+    auto next3 = [](int v) { return v == 2 ? 0 : v + 1; };
     f32x16 acc0, acc1;
-    int n = 0, slot = 0;
+    // blocks 0, 1, 2 (block n accumulates in acc0 for even n, acc1 for odd n; ring slot n % 3)
+    do_block(Generic{}, acc0, acc1, 0, 0);
+    if (cnt > 1) do_block(Generic{}, acc1, acc0, 1, 1);
+    if (cnt > 2) do_block(Generic{}, acc0, acc1, 2, 2);
+    if (cnt > 3) {
+        int n = 3, slot = 0;
+        // the steady loop: block n + 3 is issued in it, and must not be the run's last
 #pragma unroll 1
-    for (; n + 1 < cnt; n += 2) {
-        do_block(acc0, acc1, n, slot);
-        slot = slot == 2 ? 0 : slot + 1;
-        do_block(acc1, acc0, n + 1, slot);
-        slot = slot == 2 ? 0 : slot + 1;
+        for (; n + 4 < cnt; n += 2) {
+            do_block(Steady{}, acc1, acc0, n, slot);
+            slot = next3(slot);
+            do_block(Steady{}, acc0, acc1, n + 1, slot);
+            slot = next3(slot);
+        }
+        // the last one to four blocks
+        do_block(Generic{}, acc1, acc0, n, slot);
+        if (n + 1 < cnt) {
+            slot = next3(slot);
+            do_block(Generic{}, acc0, acc1, n + 1, slot);
+            if (n + 2 < cnt) {
+                slot = next3(slot);
+                do_block(Generic{}, acc1, acc0, n + 2, slot);
+                if (n + 3 < cnt) do_block(Generic{}, acc0, acc1, n + 3, next3(slot));
+            }
+        }
     }
     // (the tail reads the accumulator right behind the last MFMA; the hazard recognizer does not look inside inline asm)
-    if (n < cnt) {
-        do_block(acc0, acc1, n, slot);
-        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-        epi_split(acc0);
-    } else {
-        asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-        epi_split(acc1);
-    }
+    asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+    if (cnt & 1) epi_split(acc0);
+    else epi_split(acc1);
     epi_write();
     epi_read(0);
-    epi_store(cnt - 1, 0, 0);
+    epi_store(std::false_type{}, 0, 0);
     epi_read(1);
-    epi_store(cnt - 1, 1, 0);
+    epi_store(std::false_type{}, 1, 0);
 }
 
 }  // namespace
