@@ -592,58 +592,21 @@ int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_
         if (favor) return og_launch_favor_attention(a, st);
         return (s.flags & OG_FLAG_LINEAR_ATTENTION) ? og_launch_linear_attention(a, st) : og_launch_attention(a, st);
     };
-    // q / k / v projections of token rows [r0, r0 + R): columns [c0, c1) of the q | k | v planes = rows [c0, c1) of the packed
-    // projection matrix.  One launch; with favor_relu the feature blocks (columns < 2 WQ) carry the ReLU of the feature map and the
-    // value block does not, so a range that spans both is two launches.
-    // Few rows: proj_small_kernel (og_proj_small_wanted).
-    auto proj_small_ok = [&](int64_t R) { return L.o_wqkvs >= 0 && !favor && og_proj_small_wanted(R) && R < ((int64_t)1 << 30); };
-    auto proj_small = [&](const float* lw, int64_t r0, int64_t R, int split_row, int a0, int a1, int b0, int b1) -> int {
-        Scope sc(prof, OG_STAGE_GEMM_F16X3);
-        return og_launch_proj_small(XO + r0 * D4, D4, (int)R, D, (const char*)(lw + L.o_wqkvs), lw + L.o_bqkv, lw + L.o_scale,
-                                    QKVh + r0 * QW, QKVl + r0 * QW, QW, split_row, a0, a1, b0, b1, st);
-    };
-    // Batches (more than 8192 rows per launch) of the 128-d family: proj_stream_kernel, 128-token workgroups with the x fragments in registers and the
-    // weights through an LDS ring (mlp_fused.hip).  At D = 128 the q | k | v matrix (N = 384) has no 256-tile form and the 128-token tile GEMM runs 4
-    // k-stages per tile; at D = 256 the 256-tile GEMM stays faster in the whole step (og_proj_stream_wanted).  OG_PROJ_STREAM=0 / 1 forces.
-    // The plane rows (QW halves) are whole 128-byte lines: QW = 3D, D a multiple of 64.
-    auto proj_stream_ok = [&](int64_t R, bool full = false) {
-        return L.o_wqkvb >= 0 && !favor && og_proj_stream_wanted((int)(R < ((int64_t)1 << 30) ? R : 0), D, full) && R < ((int64_t)1 << 30) && QW % 64 == 0 &&
-               !(((uintptr_t)QKVh | (uintptr_t)QKVl) & 127);
-    };
-    auto proj_stream = [&](const float* lw, int64_t r0, int64_t R, int split_row, int a0, int a1, int b0, int b1) -> int {      // ranges in channels
-        Scope sc(prof, OG_STAGE_GEMM_F16X3);
-        return og_launch_proj_stream(XO + r0 * D4, D4, (int)R, D, (const char*)(lw + L.o_wqkvb), lw + L.o_bqkv, lw + L.o_scale,
-                                     QKVh + r0 * QW, QKVl + r0 * QW, QW, split_row, a0 / 128, a1 / 128, b0 / 128, b1 / 128, st);
-    };
-    // Batches of the 256-d family: proj_wstat_kernel (proj_wstat.hip), one 256-column slab -- q, k or v -- per workgroup with its weights in registers
-    // (the fragment-major copy proj_small_kernel reads), the token rows streaming through an LDS ring.  Uniform batches only.
-    // og_forward takes it from 8 units (32-token block x slab) per workgroup on -- 2048 units, the smallest launch it was measured at (C2's k | v of
-    // image 0: 1024 blocks x 2 slabs): a workgroup first loads 256 KB of weights, which a run of a few blocks does not pay back, so shorter launches
-    // keep the tile GEMM (the stage entry og_proj_block reaches the kernel from 8193 rows on).
-    auto proj_wstat_ok = [&](int64_t R, int64_t units) {
-        return L.o_wqkvs >= 0 && !favor && !rag && og_proj_wstat_wanted(R, D) && WQ == 256 && QW % 8 == 0 && units >= 2048;
-    };
-    auto proj_wstat = [&](const float* lw, int64_t r0, int64_t R, int split_row, int a0, int a1, int b0, int b1) -> int {      // ranges in channels
-        Scope sc(prof, OG_STAGE_GEMM_F16X3);
-        return og_launch_proj_wstat(XO + r0 * D4, D4, (int)R, (const char*)(lw + L.o_wqkvs), lw + L.o_bqkv, lw + L.o_scale, QKVh + r0 * QW, QKVl + r0 * QW,
-                                    QW, split_row, a0 / 256, a1 / 256, b0 / 256, b1 / 256, st);
-    };
-    auto qkv_proj = [&](const float* lw, int64_t r0, int64_t R, int c0, int c1) -> int {
-        if (proj_small_ok(R) && c0 % 32 == 0 && c1 % 32 == 0) return proj_small(lw, r0, R, 0, 0, 0, c0 / 32, c1 / 32);
-        if (c0 % 256 == 0 && c1 % 256 == 0 && proj_wstat_ok(R, (R + 31) / 32 * ((c1 - c0) / 256))) return proj_wstat(lw, r0, R, 0, 0, 0, c0, c1);
-        if (proj_stream_ok(R, c0 == 0 && c1 == QW) && c0 % 128 == 0 && c1 % 128 == 0 && ((r0 * QW * 2) % 128 == 0)) return proj_stream(lw, r0, R, 0, 0, 0, c0, c1);
-        const int cut = favor ? 2 * WQ : c1;
-        const int ca[2] = {c0, c0 < cut && cut < c1 ? cut : c1}, cb[2] = {ca[1], c1};
-        for (int part = 0; part < 2; ++part) {
-            const int a0 = part ? cb[0] : ca[0], a1 = part ? cb[1] : ca[1];
-            if (a1 <= a0) continue;
-            const int relu = favor && a0 < 2 * WQ;
-            if (int e = gemmh(XO + r0 * D4, lw, L.o_wqkv, a0, R, a1 - a0, D, lw + L.o_bqkv + a0, relu, nullptr, nullptr, QKVh + r0 * QW + a0,
-                              QKVl + r0 * QW + a0, QW, 0)) return e;
+    // q / k / v projections of token rows [0, R): the rows below `split` produce columns [a0, a1) of the q | k | v planes (= rows [a0, a1) of the packed
+    // projection matrix), the others [b0, b1); split = 0: every row produces [b0, b1).  og_proj_plan.h chooses the kernel family and whether the
+    // request is one launch or several; one OG_STAGE_GEMM_F16X3 scope per launch.
+    auto qkv_proj = [&](const float* lw, int64_t R, int64_t split, int a0, int a1, int b0, int b1) -> int {
+        const ProjArgs pa{XO, D4, D, (const _Float16*)(lw + L.o_wqkv), L.o_wqkvs >= 0 ? (const char*)(lw + L.o_wqkvs) : nullptr,
+                          L.o_wqkvb >= 0 ? (const char*)(lw + L.o_wqkvb) : nullptr, lw + L.o_bqkv, lw + L.o_scale, QKVh, QKVl, QW};
+        const OgProjRequest q{0, R, split, a0, a1, b0, b1, D, QW, favor ? 2 * WQ : 0, rag != nullptr, pa.wsmall != nullptr, pa.wbig != nullptr, QW,
+                              (unsigned)(((uintptr_t)QKVh | (uintptr_t)QKVl) & 127), og_proj_knobs()};
+        const OgProjPlan plan = og_proj_plan(q, OG_PROJ_FORWARD);
+        for (int i = 0; i < plan.n; ++i) {
+            Scope sc(prof, OG_STAGE_GEMM_F16X3);
+            if (int e = og_launch_proj(pa, plan.step[i], st)) return e;
         }
         return 0;
     };
-    // message MLP on token rows [r0, r0+R):  h = relu([x;O] W0'^T + b0') ; x += h W3'^T + b3'  (x kept in fp32 AND as planes)
     // message MLP on token rows [r0, r0+R):  h = relu([x;O] W0'^T + b0') ; x += h W3'^T + b3'.  x lives as hl32 (hi, lo)
     // rows (the residual is read from them: 2^-22 relative per layer); no fp32 copy is kept.
     const bool fused_mlp = og_mlp_fused_enabled(D) && L.o_wmlp >= 0;
@@ -664,7 +627,7 @@ int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_
         const float* lw = pk + L.layer0 + (int64_t)(2 * l) * L.layer_stride;
         {
             Range r_stage("gnn self", l);
-            if ((rc = qkv_proj(lw, 0, T, 0, QW))) return rc;
+            if ((rc = qkv_proj(lw, T, 0, 0, 0, 0, QW))) return rc;
             if ((rc = attention(2 * B, B, 0, m, m, 0, m, m, T0, n, n, T0, n, n, 1))) return rc;
             if ((rc = mlp(lw, 0, T))) return rc;
         }
@@ -674,34 +637,10 @@ int forward_impl(const og_shape* shape, const og_inputs* in, const void* packed_
         Range r_stage("gnn cross", l);
         for (int side = 0; side < 2; ++side) {
             const int64_t qr0 = side ? T0 : 0, qR = side ? T1 : T0;       // query rows
-            if (side == 0) {
-                // image 1 is still untouched: its k, v (for this half) and its q (for the second half) in ONE launch
-                // ... and the q of image 0 with them when the shapes allow it (whole 256-row / 256-column tiles): rows < T0 of the launch
-                // stop after the q columns.  [Two launches: 56 + 20 us at C2; one: the 512 tiles are exactly two rounds of the 256 CUs.]
-                GemmHArgs g{};
-                g.A = XO; g.lda = D4; g.B = (const _Float16*)(lw + L.o_wqkv); g.ldb = 2 * D;
-                g.M = (int)T; g.N = QW; g.K = D; g.scale = (float)(1.0 / OG_W_SCALE); g.scale_dev = lw + L.o_scale; g.bias = lw + L.o_bqkv;
-                g.Ch = QKVh; g.Cl = QKVl; g.ldch = QW; g.c_hl = 0; g.ldc = D; g.ldr = D; g.ldrh = D4;
-                g.split_row = (int)T0; g.split_n = WQ;
-                if (proj_small_ok(T) && T0 % 32 == 0 && WQ % 32 == 0) {      // rows of image 0: the q blocks only
-                    if ((rc = proj_small(lw, 0, T, (int)T0, 0, WQ / 32, 0, QW / 32))) return rc;
-                } else if (proj_stream_ok(T) && T0 % 128 == 0 && WQ % 128 == 0) {
-                    if ((rc = proj_stream(lw, 0, T, (int)T0, 0, WQ, 0, QW))) return rc;
-                } else if (!favor && !rag && T < (int64_t)1 << 30 && og_gemm_f16x3_row_split_ok(g)) {
-                    if (proj_wstat_ok(T, T0 / 32 + (T1 + 31) / 32 * 3)) {          // 256-d: the same one launch on the weight-stationary kernel
-                        if ((rc = proj_wstat(lw, 0, T, (int)T0, 0, WQ, 0, QW))) return rc;
-                    } else {
-                        Scope sc(prof, OG_STAGE_GEMM_F16X3);
-                        if ((rc = og_launch_gemm_f16x3(g, st))) return rc;
-                    }
-                } else {
-                    if ((rc = qkv_proj(lw, T0, T1, 0, QW))) return rc;
-                    if ((rc = qkv_proj(lw, 0, T0, 0, WQ))) return rc;
-                }
-            } else {
-                // k, v of the UPDATED image 0
-                if ((rc = qkv_proj(lw, 0, T0, WQ, QW))) return rc;
-            }
+            // side 0: image 1 is still untouched -- its k, v (for this half), its q (for the second half) and the q of image 0 in ONE request: the
+            // rows below T0 stop after the q columns.  [As launches of their own: 56 + 20 us at C2; one: the 512 tiles are exactly two rounds of the
+            // 256 CUs.]  Side 1: k, v of the UPDATED image 0.
+            if ((rc = side == 0 ? qkv_proj(lw, T, T0, 0, WQ, 0, QW) : qkv_proj(lw, T0, 0, 0, 0, WQ, QW))) return rc;
             if (side == 0) rc = attention(B, B, 0, m, m, T0, n, n, 0, 0, 0, 0, 0, 0, 2);
             else rc = attention(B, B, T0, n, n, 0, m, m, 0, 0, 0, 0, 0, 0, 3);
             if (rc) return rc;

@@ -1180,15 +1180,14 @@ static bool gemm_big_tile_allowed(const GemmHArgs& a, int64_t blocks) {
     const int force = og_knob_gemm_tile();
     return !a.alpha && !a.Ct && (force == 256 ? a.N >= BIG : ((a.N % BIG == 0 || a.batch > 1) && blocks >= 192 && force != 128));
 }
-// ... and the second-generation one those of a single plain problem.  The one rule of the launcher AND of og_gemm_f16x3_row_split_ok.
+// ... and the second-generation one those of a single plain problem.
 static bool gemm_big2_allowed(const GemmHArgs& a, int64_t blocks) { return gemm_big_tile_allowed(a, blocks) && og_knob_gemm_big2() && a.batch <= 1 && !a.rag; }
 
-// A row-split launch (GemmHArgs::split_row) must end up on the second-generation 256-tile kernel, with the blocks it really computes.
-bool og_gemm_f16x3_row_split_ok(const GemmHArgs& a) {
-    if (a.split_row <= 0 || a.split_row >= a.M || a.split_row % BIG || a.split_n <= 0 || a.split_n >= a.N || a.split_n % BIG) return false;
-    if (a.M % BIG || a.N % BIG || a.C32 || !a.Ch) return false;
-    const int64_t blocks = (int64_t)(a.split_row / BIG) * (a.split_n / BIG) + (int64_t)((a.M - a.split_row) / BIG) * (a.N / BIG);
-    return og_knob_gemm_row_split() && blocks >= 192 && gemm_big2_allowed(a, blocks);
+// A row-split launch (GemmHArgs::split_row) must end up on the second-generation 256-tile kernel, with the blocks it really computes:
+// og_gemm_row_split_fits (og_proj_plan.h, the rule the projection plan asks too) and what only the arguments say.
+static_assert(BIG == 256, "og_gemm_row_split_fits counts 256-row / 256-column tiles");
+static bool og_gemm_f16x3_row_split_ok(const GemmHArgs& a) {
+    return !a.C32 && a.Ch && !a.alpha && !a.Ct && a.batch <= 1 && !a.rag && og_gemm_row_split_fits(a.M, a.N, a.split_row, a.split_n, og_proj_knobs());
 }
 
 int og_launch_gemm_f16x3(const GemmHArgs& a, hipStream_t stream) {

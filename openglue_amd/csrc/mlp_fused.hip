@@ -1496,23 +1496,17 @@ bool og_pack_proj_stream(int N, int K, const double* W, void* out, double S) {
     return ok;
 }
 
-// Rows [0, M) of X (hl32 rows, x half) times columns [32 a0, 32 a1) of the packed matrix for rows below split_row, [32 b0, 32 b1) for the
-// others (split_row must be a multiple of 32 unless it is 0 or >= M); planes Ch / Cl [M][ldc].
-int og_launch_proj_small(const _Float16* X, int64_t ld, int M, int K, const char* wstream, const float* bias, const float* scale_dev,
-                         _Float16* Ch, _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream) {
-    if (!X || !wstream || !bias || !scale_dev || !Ch || !Cl || M <= 0) return OG_E_INVALID;
-    if (K != 256 && K != 128) return OG_E_SHAPE;
-    if (((uintptr_t)X & 15) || ((uintptr_t)wstream & 15) || ((uintptr_t)bias & 15) || (ld & 7) || (ldc & 3) || ((uintptr_t)Ch & 7) || ((uintptr_t)Cl & 7)) return OG_E_ALIGN;
-    if (a0 < 0 || b0 < 0 || a1 < a0 || b1 < b0 || ld < 2 * K) return OG_E_SHAPE;
-    if (split_row > 0 && split_row < M && (split_row % SM_T)) return OG_E_SHAPE;
+// One OG_PROJ_SMALL step (og_launch_proj has checked it): rows [0, s.rows) of X times columns [32 a0, 32 a1) of the packed matrix for rows below
+// split_row, [32 b0, 32 b1) for the others.
+static int launch_proj_small(const ProjArgs& a, const OgProjStep& s, hipStream_t stream) {
     // One or two pairs: a token tile's output blocks go to several workgroups, 8 blocks (one per wave) each -- nothing to reduce, and a workgroup
     // streams 256 KB of weights instead of the whole matrix (the per-CU weight stream is what bounds these kernels).
-    const int tiles = (M + SM_T - 1) / SM_T, nblk = (a1 - a0) > (b1 - b0) ? (a1 - a0) : (b1 - b0);
+    const int tiles = (s.rows + SM_T - 1) / SM_T, nblk = (s.a1 - s.a0) > (s.b1 - s.b0) ? (s.a1 - s.a0) : (s.b1 - s.b0);
     int parts = 1, bpp = nblk > 0 ? nblk : 1;
-    if (og_knob_proj_parts() &&nblk > 8 && tiles * ((nblk + 7) / 8) <= 256) { parts = (nblk + 7) / 8; bpp = 8; }
+    if (og_knob_proj_parts() && nblk > 8 && tiles * ((nblk + 7) / 8) <= 256) { parts = (nblk + 7) / 8; bpp = 8; }
     if (nblk > 24) { parts = (nblk + 7) / 8; bpp = 8; }          // a workgroup covers at most 3 blocks per wave: wider ranges are always dealt out
-    ProjSmallArgs g{X, ld, M, wstream, bias, scale_dev, Ch, Cl, ldc, split_row, a0, a1, b0, b1, parts, bpp};
-    if (K == 256) hipLaunchKernelGGL(proj_small_kernel<256>, dim3(tiles * parts), dim3(512), 0, stream, g);
+    ProjSmallArgs g{a.X, a.ld, s.rows, a.wsmall, a.bias, a.scale_dev, a.Ch, a.Cl, a.ldc, s.split_row, s.a0, s.a1, s.b0, s.b1, parts, bpp};
+    if (a.K == 256) hipLaunchKernelGGL(proj_small_kernel<256>, dim3(tiles * parts), dim3(512), 0, stream, g);
     else hipLaunchKernelGGL(proj_small_kernel<128>, dim3(tiles * parts), dim3(512), 0, stream, g);
     return og_launch_status();
 }
@@ -1545,39 +1539,41 @@ bool og_pack_proj_stream_big(int N, int K, const double* W, void* out, double S)
     return ok;
 }
 
-// og_forward: few rows (<= 8192 per launch, the single-pair regime) take proj_small_kernel, 32-token workgroups over a fragment-major copy of the
-// matrix -- 17.5 us per launch of the 128-token tile GEMM otherwise, 36 launches per step.  OG_PROJ_SMALL=0 / 1 forces.
-bool og_proj_small_wanted(int64_t R) { return og_knob_proj_small() >= 0 ? og_knob_proj_small() != 0 : R <= 8192; }
-
-// og_forward: launches of more than 8192 rows take proj_stream_kernel at K = 128 (OG_PROJ_STREAM=0 / 1 forces for both widths).  Measured in one
-// gpurun call (profiles/r05_c_proj_micro.log, r05_b_bench_proj_stream_ab.jsonl): K = 128 -- self 37.8 us against 52.6 for the 128-token tile GEMM,
-// cross 29.2 / 40.7, kv 16.8 / 21.3; C4 13.29 -> 13.12 ms, S128 12.27 -> 12.12 ms per step.  K = 256 -- self 102 us against 104.5 for the 256-tile
-// GEMM, but kv 42.6 / 33.5 and the cross launch 87.6 / ~56: C2 8.92 -> 8.99 ms, so the tile GEMMs keep the 256-d batches.
-// `full`: the launch produces every column of the matrix for all its rows (a self layer's q | k | v).  OG_PROJ_STREAM=2 (experiment): at K = 256 the stream
-// kernel takes those launches only (95 against 104.5 us in the micro-benchmark), the tile GEMMs the cross / kv forms.
-// (og_forward packs the batch stream for K = 128 only -- api.hip: packed_layout -- so forcing the K = 256 form reaches the stage entry og_proj_block alone)
-bool og_proj_stream_wanted(int M, int K, bool full) {
-    const int mode = og_knob_proj_stream();
-    if (mode == 2) return M > 8192 && (K == 128 || full);
-    if (mode >= 0) return mode != 0 && M > 0;
-    return M > 8192 && K == 128;
-}
-
-// Rows [0, M) of X (hl32 rows, x half) times columns [128 a0, 128 a1) of the packed matrix for rows below split_row, [128 b0, 128 b1) for the
-// others (split_row a multiple of 128 unless it is 0 or >= M); planes Ch / Cl [M][ldc].
-int og_launch_proj_stream(const _Float16* X, int64_t ld, int M, int K, const char* wstream, const float* bias, const float* scale_dev,
-                          _Float16* Ch, _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream) {
-    if (!X || !wstream || !bias || !scale_dev || !Ch || !Cl || M <= 0) return OG_E_INVALID;
-    if (K != 256 && K != 128) return OG_E_SHAPE;
-    if (((uintptr_t)X & 15) || ((uintptr_t)wstream & 15) || (ld & 7) || (ldc & 63) || ((uintptr_t)Ch & 127) || ((uintptr_t)Cl & 127)) return OG_E_ALIGN;
-    if (a0 < 0 || b0 < 0 || a1 < a0 || b1 < b0 || a1 - a0 > 8 || b1 - b0 > 8 || ld < 2 * K) return OG_E_SHAPE;      // (the bias area holds 1024 columns)
-    if (split_row > 0 && split_row < M && (split_row % MT)) return OG_E_SHAPE;
-    if ((int64_t)M * ld * 2 >= (int64_t)1 << 40) return OG_E_SHAPE;
-    ProjStreamArgs g{X, ld, M, wstream, bias, scale_dev, Ch, Cl, ldc, split_row, a0, a1, b0, b1};
-    const int tiles = (M + MT - 1) / MT;
-    if (K == 256) hipLaunchKernelGGL(proj_stream_kernel<256>, dim3(tiles), dim3(512), 0, stream, g);
+// One OG_PROJ_STREAM step (og_launch_proj has checked it): columns [128 a0, 128 a1) for rows below split_row, [128 b0, 128 b1) for the others.
+// Measured against the tile GEMMs in one run (profiles/r05_c_proj_micro.log, r05_b_bench_proj_stream_ab.jsonl): K = 128 -- self 37.8 us against
+// 52.6 for the 128-token tile GEMM, cross 29.2 / 40.7, kv 16.8 / 21.3; C4 13.29 -> 13.12 ms, S128 12.27 -> 12.12 ms per step.  K = 256 -- self
+// 102 us against 104.5 for the 256-tile GEMM, but kv 42.6 / 33.5 and the cross launch 87.6 / ~56: C2 8.92 -> 8.99 ms, so og_forward keeps the
+// tile GEMMs for 256-d batches (og_proj_plan.h; it packs the batch stream for K = 128 only -- api.hip: packed_layout).
+static int launch_proj_stream(const ProjArgs& a, const OgProjStep& s, hipStream_t stream) {
+    if ((int64_t)s.rows * a.ld * 2 >= (int64_t)1 << 40) return OG_E_SHAPE;
+    ProjStreamArgs g{a.X, a.ld, s.rows, a.wbig, a.bias, a.scale_dev, a.Ch, a.Cl, a.ldc, s.split_row, s.a0, s.a1, s.b0, s.b1};
+    const int tiles = (s.rows + MT - 1) / MT;
+    if (a.K == 256) hipLaunchKernelGGL(proj_stream_kernel<256>, dim3(tiles), dim3(512), 0, stream, g);
     else hipLaunchKernelGGL(proj_stream_kernel<128>, dim3(tiles), dim3(512), 0, stream, g);
     return og_launch_status();
+}
+
+// One step of a projection plan (og_proj_plan.h).  The kernels' refusals: null operands, then alignment, then shape -- what og_proj_step_check
+// says of the step plus what only the pointers tell.
+static_assert(SM_T == 32 && MT == 128, "og_proj_step_check: a row split falls between two workgroups");
+int og_launch_proj(const ProjArgs& a, const OgProjStep& s, hipStream_t stream) {
+    ProjArgs r = a;
+    r.X += s.row0 * a.ld; r.Ch += s.row0 * a.ldc; r.Cl += s.row0 * a.ldc;
+    if (s.family == OG_PROJ_GEMM) {      // columns [b0, b1) = rows [b0, b1) of the packed matrix; with split_row the rows below it stop at column a1
+        GemmHArgs g{};
+        g.A = r.X; g.lda = a.ld; g.B = a.W + (int64_t)s.b0 * 2 * a.K; g.ldb = 2 * a.K;
+        g.M = s.rows; g.N = s.b1 - s.b0; g.K = a.K; g.scale = (float)(1.0 / OG_W_SCALE); g.scale_dev = a.scale_dev; g.bias = a.bias + s.b0; g.relu = s.relu;
+        g.ldr = a.K; g.ldrh = a.ld; g.ldc = a.K;
+        g.Ch = r.Ch + s.b0; g.Cl = r.Cl + s.b0; g.ldch = a.ldc; g.c_hl = 0;
+        g.split_row = s.split_row; g.split_n = s.a1;
+        return og_launch_gemm_f16x3(g, stream);
+    }
+    const char* w = s.family == OG_PROJ_STREAM ? a.wbig : a.wsmall;
+    if (!a.X || !w || !a.bias || !a.scale_dev || !a.Ch || !a.Cl || s.rows <= 0) return OG_E_INVALID;
+    if (((uintptr_t)r.X & 15) || ((uintptr_t)w & 15) || (s.family != OG_PROJ_STREAM && ((uintptr_t)a.bias & 15)) || (a.ld & 7)) return OG_E_ALIGN;
+    if (int why = og_proj_step_check(s, a.K, a.ldc, (unsigned)(((uintptr_t)r.Ch | (uintptr_t)r.Cl) & 127))) return why;
+    if (a.ld < 2 * a.K) return OG_E_SHAPE;
+    return s.family == OG_PROJ_SMALL ? launch_proj_small(r, s, stream) : s.family == OG_PROJ_WSTAT ? og_launch_proj_wstat(r, s, stream) : launch_proj_stream(r, s, stream);
 }
 
 // og_proj_block_pack writes the small-batch stream and, when N is a multiple of 128, the batch stream right behind it
@@ -1600,19 +1596,10 @@ extern "C" int og_proj_block(const void* x_rows, int64_t ld, int32_t M, int32_t 
     og_clear_status();
     if (N <= 0 || (N % 32) || a0 < 0 || b0 < 0 || a1 < a0 || b1 < b0 || 32 * (int64_t)(a1 > b1 ? a1 : b1) > N || ldy < N) return OG_E_SHAPE;
     if (!og_proj_stream_bytes(N, K)) return OG_E_SHAPE;
-    // batches: the 128-token kernel (its stream sits behind the small one, located by N: ABI v10) when the ranges are whole 128-channel groups
-    // (the stage entry of BOTH kernels: above 8192 rows it runs proj_stream_kernel at either width, whatever og_forward prefers)
-    const int ps_mode = og_knob_proj_stream();
-    // 256-d batches whose planes are as wide as the matrix (ldy == N, og_forward's own geometry) and whose ranges are whole 256-column slabs: the
-    // weight-stationary kernel og_forward runs there (proj_wstat.hip; it reads the small-batch stream)
-    if (ps_mode < 0 && og_proj_wstat_wanted(M, K) && ldy == N && !(a0 % 8) && !(a1 % 8) && !(b0 % 8) && !(b1 % 8) && !(ldy & 7) &&
-        !(split_row > 0 && split_row < M && (split_row % 32)) && !((uintptr_t)yh & 15) && !((uintptr_t)yl & 15))
-        return og_launch_proj_wstat((const _Float16*)x_rows, ld, M, (const char*)stream_dev, bias, inv_scale_dev, (_Float16*)yh, (_Float16*)yl, ldy, split_row,
-                                    a0 / 8, a1 / 8, b0 / 8, b1 / 8, (hipStream_t)stream);
-    if ((ps_mode >= 0 ? ps_mode != 0 : M > 8192) && og_proj_stream_big_bytes(N, K) && !(a0 % 4) && !(a1 % 4) && !(b0 % 4) && !(b1 % 4) && a1 - a0 <= 32 && b1 - b0 <= 32 &&
-        !(ldy & 63) && !(split_row > 0 && split_row < M && (split_row % MT)) && !((uintptr_t)yh & 127) && !((uintptr_t)yl & 127))
-        return og_launch_proj_stream((const _Float16*)x_rows, ld, M, K, (const char*)stream_dev + og_proj_stream_bytes(N, K), bias, inv_scale_dev,
-                                     (_Float16*)yh, (_Float16*)yl, ldy, split_row, a0 / 4, a1 / 4, b0 / 4, b1 / 4, (hipStream_t)stream);
-    return og_launch_proj_small((const _Float16*)x_rows, ld, M, K, (const char*)stream_dev, bias, inv_scale_dev, (_Float16*)yh, (_Float16*)yl, ldy,
-                                split_row, a0, a1, b0, b1, (hipStream_t)stream);
+    // the stage entry of EVERY projection kernel (og_proj_plan.h: OG_PROJ_STAGE_ENTRY); the batch stream sits behind the small one, located by N (ABI v10)
+    ProjArgs pa{(const _Float16*)x_rows, ld, K, nullptr, (const char*)stream_dev, nullptr, bias, inv_scale_dev, (_Float16*)yh, (_Float16*)yl, ldy};
+    if (og_proj_stream_big_bytes(N, K)) pa.wbig = pa.wsmall + og_proj_stream_bytes(N, K);
+    const OgProjRequest q{0, M, split_row, 32 * a0, 32 * a1, 32 * b0, 32 * b1, K, N, 0, false, true, pa.wbig != nullptr, ldy,
+                          (unsigned)(((uintptr_t)yh | (uintptr_t)yl) & 127), og_proj_knobs()};
+    return og_launch_proj(pa, og_proj_plan(q, OG_PROJ_STAGE_ENTRY).step[0], (hipStream_t)stream);      // one step, always
 }

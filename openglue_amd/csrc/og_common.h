@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include "../../include/openglue_amd.h"
 #include "og_knobs.h"      // the OG_* environment knobs: one accessor each
+#include "og_proj_plan.h"  // the q | k | v projection: request -> launches (plain C++)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -182,10 +183,9 @@ struct GemmHArgs {
                                               // (A rows off0[z].., B rows T0 + off1[z].., M = m_z, N = n_z; C32 at z*strideC32)
     int split_row, split_n;                   // split_row > 0: rows < split_row produce only columns < split_n (two row ranges with different
                                               // column counts in ONE launch: the cross layer's q of image 0 + q | k | v of image 1).  Only the
-                                              // 256-tile kernel honours it: og_gemm_f16x3_row_split_ok() tells whether a launch qualifies.
+                                              // 256-tile kernel honours it, for launches that pass og_gemm_row_split_fits() (og_proj_plan.h).
 };
 int og_launch_gemm_f16x3(const GemmHArgs& a, hipStream_t stream);
-bool og_gemm_f16x3_row_split_ok(const GemmHArgs& a);
 int og_launch_split_f16(const float* x, int64_t n, void* hi, void* lo, hipStream_t stream);
 int og_launch_split_f16_hl(const float* x, int64_t rows, int cols, int64_t ldx, void* out, int64_t ldo, hipStream_t stream);
 int og_launch_merge_f16_hl(const void* in, int64_t rows, int cols, int64_t ldi, float* out, int64_t ldo, hipStream_t stream);
@@ -209,20 +209,22 @@ bool og_mlp_small_wanted(int M);
 // the q / k / v projections for few token rows (mlp_fused.hip: proj_small_kernel), a fragment-major copy of the packed matrix
 size_t og_proj_stream_bytes(int N, int K);
 bool og_pack_proj_stream(int N, int K, const double* W, void* out, double S);
-bool og_proj_small_wanted(int64_t R);                     // og_forward's choice: at most 8192 rows per launch (OG_PROJ_SMALL forces)
 // ... and for batches (mlp_fused.hip: proj_stream_kernel, 128-token workgroups, x fragments in registers, the weights through an LDS ring)
 size_t og_proj_stream_big_bytes(int N, int K);
 bool og_pack_proj_stream_big(int N, int K, const double* W, void* out, double S);
-bool og_proj_stream_wanted(int M, int K, bool full);      // og_forward's choice: K = 128 batches (OG_PROJ_STREAM forces)
-int og_launch_proj_stream(const _Float16* X, int64_t ld, int M, int K, const char* wstream, const float* bias, const float* scale_dev,
-                          _Float16* Ch, _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream);   // ranges in units of 128 channels
-int og_launch_proj_small(const _Float16* X, int64_t ld, int M, int K, const char* wstream, const float* bias, const float* scale_dev,
-                         _Float16* Ch, _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream);
-// ... and for 256-d batches (proj_wstat.hip: proj_wstat_kernel, one 256-column slab per workgroup, the weights in registers, the tokens through an
-// LDS ring).  It reads the SAME stream as proj_small_kernel (og_pack_proj_stream: one 1 KiB A fragment per load).  Ranges in slabs of 256 columns.
-bool og_proj_wstat_wanted(int64_t M, int K);                  // more than 8192 rows at K = 256
-int og_launch_proj_wstat(const _Float16* X, int64_t ld, int M, const char* wstream, const float* bias, const float* scale_dev, _Float16* Ch,
-                         _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream);
+// One q | k | v projection request: the operands every kernel family reads.  og_proj_plan (og_proj_plan.h) chooses the launches, og_launch_proj runs one.
+struct ProjArgs {
+    const _Float16* X; int64_t ld;      // hl32 rows (x half) of ALL token rows of the request's numbering, row stride ld halves
+    int K;
+    const _Float16* W;                  // the packed matrix as hl32 rows (the tile GEMM; null: no GEMM step can run)
+    const char* wsmall;                 // og_pack_proj_stream (proj_small_kernel, proj_wstat_kernel)
+    const char* wbig;                   // og_pack_proj_stream_big (proj_stream_kernel)
+    const float* bias; const float* scale_dev;
+    _Float16* Ch; _Float16* Cl; int64_t ldc;      // planes [rows][ldc]
+};
+inline OgProjKnobs og_proj_knobs() { return {og_knob_proj_small(), og_knob_proj_stream(), og_knob_gemm_row_split(), og_knob_gemm_tile(), og_knob_gemm_big2()}; }
+int og_launch_proj(const ProjArgs& a, const OgProjStep& s, hipStream_t stream);            // mlp_fused.hip; OG_E_* where og_proj_step_check refuses the step
+int og_launch_proj_wstat(const ProjArgs& a, const OgProjStep& s, hipStream_t stream);      // proj_wstat.hip (called by og_launch_proj)
 
 constexpr int OG_ATTN_COUNTERS = 256;                                   // (problem, head, query tile) triples of a key-split launch
 constexpr int64_t OG_ATTN_PARTIAL_FLOATS = (int64_t)512 * 4 * 34 * 64;     // 512 workgroups (two per CU) x 4 waves x (32 O registers + m + l) x 64 lanes

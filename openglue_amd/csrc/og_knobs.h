@@ -2,7 +2,8 @@
 // One parser: a knob is unset or a decimal integer (strtoll: "" and text without leading digits read as 0).  A switch is "value != 0"; a mode
 // knob is -1 (unset or negative: the launcher's own rule) or the forced value.  CACHED knobs are read once per process (a test that switches
 // one starts a child process), LIVE knobs at every call (tests switch them within one process).  The derived predicates (og_mlp_fused_enabled,
-// og_mlp_small_wanted, og_proj_small_wanted, og_proj_stream_wanted, ...) stay beside their kernels and call these accessors.
+// og_mlp_small_wanted, ...) stay beside their kernels and call these accessors; the q | k | v projection plan (og_proj_plan.h, plain C++ that a
+// host-only program runs) takes the values of its knobs as plain ints from og_proj_knobs() (og_common.h).
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -14,6 +15,7 @@ inline long long og_knob_value(const char* name, long long unset) { long long v;
 
 // ---- api.hip ----
 OG_KNOB_CACHED(bool, og_knob_roctx, "OG_ROCTX", 0)                            // 1: every og_forward* call pushes / pops named roctx ranges
+// ---- og_proj_plan.h (with OG_PROJ_STREAM, OG_GEMM_ROW_SPLIT, OG_GEMM_TILE, OG_GEMM_BIG2 below) ----
 OG_KNOB_CACHED(int, og_knob_proj_small, "OG_PROJ_SMALL", -1)                  // 0 / 1 forces proj_small_kernel off / on (default: <= 8192 rows per launch)
 // ---- gemm_f16x3.hip, gemm_f32.hip (experiments) ----
 OG_KNOB_CACHED(int, og_knob_gemm_tile, "OG_GEMM_TILE", 0)                     // 128 / 256 forces the tile family

@@ -309,19 +309,10 @@ __global__ __launch_bounds__(512) void proj_wstat_kernel(ProjWstatArgs g) {
 
 }  // namespace
 
-bool og_proj_wstat_wanted(int64_t M, int K) { return K == 256 && M > 8192 && M < ((int64_t)1 << 30); }
-
-// Rows [0, M) of X (hl32 rows, x half, K = 256) times the 256-column slabs [a0, a1) of the packed matrix for the rows below split_row,
-// [b0, b1) for the others (split_row a multiple of 32 unless it is <= 0 or >= M: then every row takes the second / the first range);
-// planes Ch / Cl [M][ldc].  wstream: og_pack_proj_stream of the matrix.
-int og_launch_proj_wstat(const _Float16* X, int64_t ld, int M, const char* wstream, const float* bias, const float* scale_dev, _Float16* Ch,
-                         _Float16* Cl, int64_t ldc, int split_row, int a0, int a1, int b0, int b1, hipStream_t stream) {
-    if (!X || !wstream || !bias || !scale_dev || !Ch || !Cl || M <= 0) return OG_E_INVALID;
-    if (((uintptr_t)X & 15) || ((uintptr_t)wstream & 15) || ((uintptr_t)bias & 15) || (ld & 7) || (ldc & 7) || ((uintptr_t)Ch & 15) || ((uintptr_t)Cl & 15))
-        return OG_E_ALIGN;
-    if (a0 < 0 || b0 < 0 || a1 < a0 || b1 < b0 || ld < 512 || ldc < 256 * (int64_t)(a1 > b1 ? a1 : b1)) return OG_E_SHAPE;
-    if (split_row > 0 && split_row < M && (split_row % WS_BLK)) return OG_E_SHAPE;
-    ProjWstatArgs g{X, ld, M, wstream, bias, scale_dev, Ch, Cl, ldc, a0, b0, og_proj_deal_rows(M, split_row, a1 - a0, b1 - b0, WS_G)};
+// One OG_PROJ_WSTAT step (og_launch_proj has checked it): rows [0, s.rows) of X times the 256-column slabs [a0, a1) of the packed matrix for the
+// rows below split_row, [b0, b1) for the others (split_row <= 0 or >= rows: every row takes the second / the first range).
+int og_launch_proj_wstat(const ProjArgs& a, const OgProjStep& s, hipStream_t stream) {
+    ProjWstatArgs g{a.X, a.ld, s.rows, a.wsmall, a.bias, a.scale_dev, a.Ch, a.Cl, a.ldc, s.a0, s.b0, og_proj_deal_rows(s.rows, s.split_row, s.a1 - s.a0, s.b1 - s.b0, WS_G)};
     if (g.deal.ta * g.deal.na + g.deal.tb * g.deal.nb == 0) return 0;       // both ranges empty: nothing to write
     hipLaunchKernelGGL(proj_wstat_kernel, dim3(WS_G), dim3(512), 0, stream, g);
     return og_launch_status();

@@ -81,6 +81,12 @@ def proj_mlp_instances(names) -> list:
     return [n for n in names if n.startswith(PROJ_MLP)]
 
 
+def projection_candidates(names) -> list:
+    """Every launch among `names` that can be a q | k | v projection or sits between two of them in og_forward's GNN -- the message-MLP and projection
+    kernels of csrc/mlp_fused.hip, proj_wstat_kernel, the split-f16 GEMM instances -- in launch order, one entry per launch."""
+    return [n for n in names if n.startswith(PROJ_MLP + ("gemm_nt_f16x3_",)) or n == PROJ_WSTAT]
+
+
 def attention_train_instances(names) -> list:
     """The softmax-attention training launches (csrc/attention_train.hip: backward, row log-sum-exp, delta) among `names`, in launch order."""
     return [n for n in names if n.startswith(ATTENTION_TRAIN)]

@@ -10,7 +10,7 @@ MLP, through ops.mlp_block (asserting that mlp_fused_kernel<D> ran):
   does not depend on what lies behind row M - 1 (clamped loads, predicated stores, the peeled stages).
 
 Projection, through og_proj_block (asserting that proj_wstat_kernel ran and nothing else): the smallest row counts that reach the kernel
-(og_proj_wstat_wanted: more than 8192 rows) -- 8224, 8193, 8223, i.e. M % 32 = 0, 1, 31, all 257 blocks -- as a 3-slab launch (85 teams: runs
+(og_proj_plan.h: more than 8192 rows) -- 8224, 8193, 8223, i.e. M % 32 = 0, 1, 31, all 257 blocks -- as a 3-slab launch (85 teams: runs
 of 3 and 4 blocks), a 2-slab launch (k | v; 128 teams: runs of 2 and 3) and a row-split launch (q for the rows below 2720, q | k | v for the
 others); a port of og_proj_deal (csrc/og_proj_deal.h) asserts that runs of odd AND even length occur in every case.  Those runs end inside
 the generic first / last blocks of the kernel, so one more 3-slab case, 24481 rows (766 blocks: runs of 9 and 10), goes through the steady

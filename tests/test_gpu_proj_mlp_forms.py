@@ -1,13 +1,13 @@
 """Every q | k | v projection and message-MLP form the default dispatch launches (csrc/mlp_fused.hip), pinned to float64 on EVERY output
 element, with the launched instance asserted.
 
-og_launch_mlp_fused, og_proj_block / og_launch_proj_small / og_launch_proj_stream and og_forward's own routing (csrc/api.hip) pick one of
-four kernels at two widths from the row count, the alignment of the biases, the column ranges, the leading dimension and alignment of
-the output planes and the row split.  The functions of section 0 restate those rules; every GPU case asserts that the launches it made
-are exactly the predicted ones, so a case cannot drift onto another kernel unnoticed.  `parts` / `bpp` (how og_launch_proj_small deals
-the output blocks of a token tile out to workgroups) and the per-wave block count cannot be observed from the kernel name: their
-restatement (`proj_small_grid`, `wave_blocks`) is there to prove that each shape sits on the intended side of a threshold, and the
-case ids carry what it predicts.
+og_launch_mlp_fused and the projection plan (csrc/og_proj_plan.h, under og_proj_block's and og_forward's policy) pick the kernel from the row
+count, the alignment of the biases, the column ranges, the leading dimension and alignment of the output planes and the row split.
+tests/proj_plan_ref.py restates those rules (from the call sites as they stood before the plan header; tests/test_proj_plan_cpu.py holds the
+header to it); every GPU case asserts that the launches it made are exactly the predicted ones, so a case cannot drift onto another kernel
+unnoticed.  `parts` / `bpp` (how proj_small_kernel's launch deals the output blocks of a token tile out to workgroups) and the per-wave
+block count cannot be observed from the kernel name: their restatement (`proj_small_grid`, `wave_blocks`, section 0) is there to prove
+that each shape sits on the intended side of a threshold, and the case ids carry what it predicts.
 
   0. the restatement itself, on both sides of every boundary (CPU)
   1. the message MLP through _lib (og_mlp_block_pack, og_mlp_block), D = 256 / 128: rows of ld = 4D + 8 halves with NaN in the gap of every
@@ -19,8 +19,8 @@ case ids carry what it predicts.
      sides of the deal-out rule, ranges that start in the middle of the matrix, the row split (also with an empty range and with
      split_row >= M), the forced deal-out with a ragged last part.  proj_stream_kernel: partial last tiles, every group position, the row
      split, the widest range it takes.  The fall-backs of the stage entry to proj_small_kernel above 8192 rows, the refusals
-  3. the forms og_forward launches, through SuperGlue (one stage): the multiset of the four kernels in one traced call against the
-     restatement, x at tap 1 against the float64 oracle's self layer applied to tap 0, x at tap 2 against its cross layer applied to
+  3. the forms og_forward launches, through SuperGlue (one stage): EVERY projection and message-MLP launch of one traced call, in launch
+     order -- the kernels of mlp_fused.hip, proj_wstat_kernel and the tile GEMMs a projection falls to -- against the restatement, x at tap 1 against the float64 oracle's self layer applied to tap 0, x at tap 2 against its cross layer applied to
      tap 1.  One case gives the three split-f16 matrices of each layer three DIFFERENT power-of-two pre-scales (read back from the packed
      blob and asserted pairwise different first): the only place MlpFusedArgs::scales_dev is pinned at a layer
 
@@ -38,10 +38,12 @@ instance -> a case that asserts it
   proj_small_kernel<128>    test_proj_small_full[128-*], test_proj_small_ranges[K128-*], test_proj_small_row_split[128-*], test_proj_fall_backs[128-*]
   proj_stream_kernel<256>   test_proj_stream_full[256-*], test_proj_stream_groups[256-*], test_proj_stream_row_split[256-*], test_proj_stream_widest[256]
   proj_stream_kernel<128>   test_proj_stream_full[128-*], test_proj_stream_groups[128-*], test_proj_stream_row_split[128-*], test_forward_forms[d128-*]
+  proj_wstat_kernel         test_forward_forms[d256-B12-*] (a self launch), [d256-B16-*] (self, the row split, k | v); tests/test_gpu_proj_wstat.py pins its values
 not covered, and why:
   OG_PROJ_PARTS=0                           one workgroup per token tile whatever the shape: an experiment knob, read once per process
-  OG_PROJ_STREAM=2 (and 0 / 1)              the stream kernel for a self layer's launches at K = 256 / forced on or off: experiments
-  OG_MLP_FUSED=0, OG_MLP_SMALL, OG_PROJ_SMALL   fc.0 / fc.3 as two GEMM launches, forced kernel choices: experiments; the GEMM forms are
+  OG_PROJ_STREAM, OG_PROJ_SMALL             forced kernel choices (experiments, read once per process): which launches they move is checked
+                                            without a GPU (tests/test_proj_plan_cpu.py); the kernels they move them to are pinned here
+  OG_MLP_FUSED=0, OG_MLP_SMALL              fc.0 / fc.3 as two GEMM launches, a forced kernel choice: experiments; the GEMM forms are
                                             pinned in tests/test_gpu_gemm_forms.py
   proj_stream_kernel<256> under og_forward  og_forward packs the batch stream at D = 128 only (api.hip: packed_layout); the K = 256 form
                                             is reachable through the stage entry alone (section 2)
@@ -52,15 +54,15 @@ not covered, and why:
 """
 import functools
 import os
-from collections import Counter
 
 import pytest
 import torch
 
 from openglue_amd import _lib, ops, synthetic as syn
-from openglue_amd.kernel_trace import launched_kernels, proj_mlp_instances
+from openglue_amd.kernel_trace import launched_kernels, proj_mlp_instances, projection_candidates
 from oracle import superglue_oracle as orc
 from tests.test_gpu_gemm_forms import NAN, SENT, TOL_TAP, _dev, _stop_after_a_gpu_fault  # noqa: F401  (the fixture is autouse here too)
+from tests.proj_plan_ref import expected_forward, expected_mlp, expected_proj_block, forward_sequence
 from tests.util import to_device
 
 # The dispatch knobs are read once per process: one left in the environment would move every case below to another kernel.
@@ -76,24 +78,8 @@ def _cdiv(a, b):
 
 
 # ----------------------------------------------------------------------------- 0. the selection rules, restated
-def expected_mlp(M, D, b0_aligned=True, b3_aligned=True):
-    """og_launch_mlp_fused (mlp_fused.hip): 32-token workgroups up to 8192 rows (og_mlp_small_wanted) when both
-    biases can be read as 16-byte vectors, the 128-token tile kernel otherwise."""
-    small = M <= 8192 and b0_aligned and b3_aligned
-    return f"mlp_small_kernel<{D}>" if small else f"mlp_fused_kernel<{D}>"
-
-
-def expected_proj_block(M, K, N, a, b, ldy, split_row=0, planes_aligned=True):
-    """og_proj_block (mlp_fused.hip).  a, b: block ranges (units of 32 channels) of the rows below / from split_row."""
-    stream = (M > 8192 and N % 128 == 0                                                        # more than 8192 rows, a batch stream exists
-              and all(v % 4 == 0 for v in (*a, *b)) and a[1] - a[0] <= 32 and b[1] - b[0] <= 32     # whole 128-channel groups, at most 8 of them
-              and ldy % 64 == 0 and not (0 < split_row < M and split_row % 128)                # plane rows of whole lines, a tile-aligned split
-              and planes_aligned)                                                              # 128-byte aligned planes
-    return f"proj_stream_kernel<{K}>" if stream else f"proj_small_kernel<{K}>"
-
-
 def proj_small_grid(M, a, b):
-    """og_launch_proj_small (mlp_fused.hip) -> (parts, bpp, workgroups)."""
+    """launch_proj_small (mlp_fused.hip) -> (parts, bpp, workgroups)."""
     tiles, nblk = _cdiv(M, 32), max(a[1] - a[0], b[1] - b[0])
     parts, bpp = 1, max(nblk, 1)
     if nblk > 8 and tiles * _cdiv(nblk, 8) <= 256:         # few tiles: 8 blocks (one per wave) per workgroup
@@ -122,42 +108,6 @@ def proj_small_forms(M, a, b, split_row=0):
     return parts, bpp, sorted(nb)
 
 
-def expected_forward(D, B, m, n, stages=1):
-    """og_forward's routing of the q | k | v projections and the message MLP (api.hip: forward_impl) for softmax attention: the multiset of the
-    four kernels of mlp_fused.hip over `stages` self + cross layers.  Launches that go to the tile GEMMs are not counted here
-    (tests/test_gpu_gemm_forms.py pins those)."""
-    T0, T1, QW = B * m, B * n, 3 * D
-    T = T0 + T1
-    ps, pst = f"proj_small_kernel<{D}>", f"proj_stream_kernel<{D}>"
-    c = Counter()
-    small_ok = lambda R: R <= 8192                                         # og_proj_small_wanted (a fragment-major copy exists at D = 256 / 128)
-    stream_ok = lambda R: R > 8192 and D == 128                            # og_proj_stream_wanted
-
-    def qkv(r0, R, c0, c1):
-        if small_ok(R) and c0 % 32 == 0 and c1 % 32 == 0:
-            c[ps] += 1
-        elif stream_ok(R) and c0 % 128 == 0 and c1 % 128 == 0 and (r0 * QW * 2) % 128 == 0:
-            c[pst] += 1
-
-    def mlp(R):                                                            # the packed biases start 256-byte aligned sections
-        c[expected_mlp(R, D)] += 1
-
-    for _ in range(stages):
-        qkv(0, T, 0, QW); mlp(T)                                           # self layer: both images in one launch each
-        if small_ok(T) and T0 % 32 == 0:                                   # one proj_small launch with a row split
-            c[ps] += 1
-        elif stream_ok(T) and T0 % 128 == 0 and D % 128 == 0:              # one proj_stream launch with a row split
-            c[pst] += 1
-        elif D % 256 == 0 and T0 % 256 == 0 and T % 256 == 0 and T0 // 256 + (T1 // 256) * (QW // 256) >= 192:
-            pass                                                           # the 256-tile GEMM with a row split (og_gemm_f16x3_row_split_ok)
-        else:
-            qkv(T0, T1, 0, QW); qkv(0, T0, 0, D)
-        mlp(T0)                                                            # side 0
-        qkv(0, T0, D, QW)                                                  # k | v of the updated image 0
-        mlp(T1)                                                            # side 1
-    return c
-
-
 def test_restatement_sides_of_the_boundaries():
     """The boundaries of the launchers and of og_forward's routing as the restatement sees them (a wrong restatement would make every
     assertion below pointless)."""
@@ -178,7 +128,7 @@ def test_restatement_sides_of_the_boundaries():
         assert expected_proj_block(8320, D, 3 * D, (0, D // 32), (0, 3 * D // 32), 3 * D + 64, split_row=8224) == ps
         assert expected_proj_block(8320, D, 3 * D, (0, D // 32), (0, 3 * D // 32), 3 * D + 64, split_row=8320) == pst    # split_row >= M
         assert expected_proj_block(8193, D, 3 * D, *full(3 * D), 3 * D + 64, planes_aligned=False) == ps
-    # og_launch_proj_small: tiles * parts <= 256 at 24 blocks (3 parts) and at 12 (2 parts); 8 / 9 blocks; 24 / 25 blocks
+    # launch_proj_small: tiles * parts <= 256 at 24 blocks (3 parts) and at 12 (2 parts); 8 / 9 blocks; 24 / 25 blocks
     assert proj_small_grid(2720, (0, 0), (0, 24)) == (3, 8, 255) and proj_small_grid(2721, (0, 0), (0, 24)) == (1, 24, 86)
     assert proj_small_grid(4096, (0, 0), (0, 12)) == (2, 8, 256) and proj_small_grid(4097, (0, 0), (0, 12)) == (1, 12, 129)
     assert proj_small_grid(96, (0, 0), (0, 8)) == (1, 8, 3) and proj_small_grid(96, (0, 0), (0, 9)) == (2, 8, 6)
@@ -207,6 +157,22 @@ def test_restatement_sides_of_the_boundaries():
     assert expected_forward(128, 1, 128, 8064) == {ps: 3, ms: 3}                         # T = 8192
     assert expected_forward(128, 1, 128, 8065) == {pst: 2, ps: 1, mf: 1, ms: 2}          # T = 8193
     assert expected_forward(128, 1, 128, 160) == {ps: 3, ms: 3} and expected_forward(128, 1, 130, 97) == {ps: 4, ms: 3}
+    # the stage entry reaches proj_wstat_kernel where the planes are as wide as the matrix: 8192 / 8193 rows, ldy, a range of whole slabs or not
+    assert expected_proj_block(8193, 256, 768, *full(768), 768) == "proj_wstat_kernel" and expected_proj_block(8192, 256, 768, *full(768), 768) == "proj_small_kernel<256>"
+    assert expected_proj_block(8193, 256, 768, *full(768), 768 + 64) == "proj_stream_kernel<256>" and expected_proj_block(8193, 128, 384, *full(384), 384) == "proj_stream_kernel<128>"
+    assert expected_proj_block(8193, 256, 768, (0, 0), (4, 24), 768) == "proj_stream_kernel<256>" and expected_proj_block(8193, 256, 768, (0, 0), (8, 24), 768) == "proj_wstat_kernel"
+    # og_forward's 256-d batches, in launch order: the 2048-unit floor of proj_wstat_kernel and the 192 big tiles of the row-split GEMM
+    wst, big2, t128 = "proj_wstat_kernel", "gemm_nt_f16x3_big2_kernel<2, 1>", "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 2, 1>"
+    ms, mf, ps, pst = k(256)
+    assert forward_sequence(256, 12, 1024, 1024) == [wst, mf, big2, mf, t128, mf]        # 2304 units | 1536 units, 192 big tiles | 768 units, 96 big tiles
+    assert forward_sequence(256, 16, 1024, 1024) == [wst, mf, wst, mf, t128, mf]         # the cross launch: 512 + 1536 = 2048 units; k | v: 1024 units, 128 big tiles
+    gen = "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 0, 0>"
+    assert forward_sequence(256, 2, 128, 4100) == [gen, mf, gen, ps, ms, ps, mf]         # T = 8456, image 1 = 8200 rows: GEMMs of a partial last tile
+    assert forward_sequence(256, 8, 0, 0, lens=RAGGED_LENS) == [big2, mf, big2, ps, ms, ps, mf]      # uniform, T0 = 512 and T1 = 22016 would give [wst, mf, wst, ms, ps, mf]
+    assert forward_sequence(256, 1, 512, 22016) == [wst, mf, wst, ms, ps, mf]
+    relu, plain = "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 0, 0>", "gemm_nt_f16x3_kernel<128, 2, RaggedNone, 2, 1>"
+    assert forward_sequence(128, 1, 128, 128, favor=True) == [relu, plain, "mlp_small_kernel<128>", relu, plain, relu, "mlp_small_kernel<128>", relu, plain,
+                                                              "mlp_small_kernel<128>"]
 
 
 # ----------------------------------------------------------------------------- shared plumbing of the GPU cases
@@ -451,7 +417,7 @@ def test_proj_small_full(gpu_device, K, M):
 @gpu
 @pytest.mark.parametrize("K,M,parts", [(256, 2720, 3), (256, 2721, 1), (128, 4096, 2), (128, 4097, 1)])
 def test_proj_small_deal_out_threshold(gpu_device, K, M, parts):
-    """Both sides of tiles * parts <= 256 (og_launch_proj_small) on the whole q | k | v matrix: 85 x 3 / 86 x 3 at 24 blocks, 128 x 2 / 129 x 2 at
+    """Both sides of tiles * parts <= 256 (launch_proj_small) on the whole q | k | v matrix: 85 x 3 / 86 x 3 at 24 blocks, 128 x 2 / 129 x 2 at
     12.  Not dealt out, a wave owns 3 blocks (K = 256) or 2 / 1 (K = 128)."""
     N = 3 * K
     assert proj_small_grid(M, *_full(N))[0] == parts
@@ -528,7 +494,7 @@ def test_proj_stream_row_split(gpu_device, K, split):
 @gpu
 @pytest.mark.parametrize("K", [256, 128])
 def test_proj_stream_widest(gpu_device, K):
-    """N = 1024: 8 groups, the most og_launch_proj_stream takes (its bias area holds 1024 columns)."""
+    """N = 1024: 8 groups, the most proj_stream_kernel takes (og_proj_step_check) (its bias area holds 1024 columns)."""
     _proj_case(8193, K, 1024, *_full(1024), f"proj_stream_kernel<{K}>")
 
 
@@ -556,7 +522,7 @@ def test_proj_fall_backs(gpu_device, K, why):
 @pytest.mark.parametrize("what,code", [("split_33", OG_E_SHAPE), ("bias_off", OG_E_ALIGN), ("ld_short", OG_E_SHAPE), ("range_past_n", OG_E_SHAPE)])
 @pytest.mark.parametrize("K", [256, 128])
 def test_proj_refusals(gpu_device, K, what, code):
-    """og_proj_block / og_launch_proj_small return before any launch: the error code, and both planes as they were."""
+    """og_proj_block / og_launch_proj return before any launch: the error code, and both planes as they were."""
     M, N = 96, 3 * K
     w, d = _proj_weights(N, K), _proj_data(M, N, K)
     X = _proj_x(d, M, K)
@@ -573,9 +539,9 @@ def test_proj_refusals(gpu_device, K, what, code):
 
 
 # ----------------------------------------------------------------------------- 3. the forms og_forward launches
-def _model(D, tweak=None):
+def _model(D, tweak=None, heads=4, attention="softmax", iters=2):
     from tests.test_gpu_parity import _build
-    cfg = syn.make_config(descriptor_dim=D, num_stages=1, num_heads=4, num_iters=2, side_info_size=1, residual=True)
+    cfg = syn.make_config(descriptor_dim=D, num_stages=1, num_heads=heads, num_iters=iters, side_info_size=1, residual=True, attention=attention)
     sd = syn.make_state_dict(cfg, seed=0)
     if tweak is not None:
         tweak(sd, D)
@@ -601,11 +567,11 @@ def _distinct_prescales(sd, D):
         sd[f"{p}.fc.3.weight"][11, o, 0] = 700.0 / gain            # 64 x 700 > 32768 >= 32 x 700 after the BatchNorm fold
 
 
-def _layer64(sd, H, l, x0, x1):
+def _layer64(sd, H, l, x0, x1, attention="softmax"):
     """attention_gnn.layers[l] in float64 on [B, m, D], [B, n, D] (attention_gnn.py:63-77), one pair at a time (a 4100 x 4100 attention matrix
     per head is 134 MB)."""
     p = f"attention_gnn.layers.{l}.module"
-    mp = lambda q, kv: torch.cat([orc.message_passing(q[i:i + 1], kv[i:i + 1], sd, p, H, False) for i in range(q.shape[0])])
+    mp = lambda q, kv: torch.cat([orc.message_passing(q[i:i + 1], kv[i:i + 1], sd, p, H, False, attention=attention) for i in range(q.shape[0])])
     with torch.no_grad():
         if l % 2 == 0:
             return mp(x0, x0), mp(x1, x1)
@@ -613,24 +579,43 @@ def _layer64(sd, H, l, x0, x1):
         return r0, mp(x1, r0)                                      # image 1 against the UPDATED image 0
 
 
-FORWARD_CASES = [pytest.param(128, 2, 128, 4100, False, id="d128-B2-m128-n4100"), pytest.param(128, 2, 130, 4100, False, id="d128-B2-m130-n4100"),
-                 pytest.param(256, 1, 128, 160, False, id="d256-B1-m128-n160"), pytest.param(256, 1, 130, 97, False, id="d256-B1-m130-n97"),
-                 pytest.param(256, 2, 128, 4100, False, id="d256-B2-m128-n4100"), pytest.param(128, 2, 128, 4100, True, id="d128-B2-m128-n4100-prescales")]
+FORWARD_CASES = [pytest.param(128, 2, 128, 4100, None, id="d128-B2-m128-n4100"), pytest.param(128, 2, 130, 4100, None, id="d128-B2-m130-n4100"),
+                 pytest.param(256, 1, 128, 160, None, id="d256-B1-m128-n160"), pytest.param(256, 1, 130, 97, None, id="d256-B1-m130-n97"),
+                 pytest.param(256, 2, 128, 4100, None, id="d256-B2-m128-n4100"), pytest.param(128, 2, 128, 4100, "prescales", id="d128-B2-m128-n4100-prescales"),
+                 pytest.param(256, 12, 1024, 1024, None, id="d256-B12-m1024-n1024"), pytest.param(256, 16, 1024, 1024, None, id="d256-B16-m1024-n1024"),
+                 pytest.param(128, 1, 128, 128, "favor", id="d128-B1-m128-n128-favor_relu")]
+ENC_TAIL, TAIL = 2, 3        # split-f16 GEMM launches of a forward in front of the GNN (the last encoder conv, per image: hidden width 128 <= D) and behind it
+                             # (the final projection per image, the score matrix)
+RAGGED_LENS = ([40, 88, 64, 64, 100, 28, 64, 64], [2752, 2700, 2804, 2752, 2600, 2904, 2752, 2752])      # T0 = 512, T1 = 22016
+
+
+def _gnn_launches(fn, D):
+    """-> every projection and message-MLP launch of the GNN of one traced forward, in launch order (the GEMMs around the GNN checked and cut off)."""
+    seq = projection_candidates(launched_kernels(fn))
+    assert len(seq) > ENC_TAIL + TAIL and all(k.startswith("gemm_nt_f16x3_") for k in seq[:ENC_TAIL] + seq[-TAIL:]), seq
+    return seq[ENC_TAIL:-TAIL]
 
 
 @gpu
-@pytest.mark.parametrize("D,B,m,n,prescales", FORWARD_CASES)
-def test_forward_forms(gpu_device, D, B, m, n, prescales):
-    """One stage of og_forward: the launches of the four kernels against the restatement, then x after the self layer and after the cross
-    layer against float64 of that layer applied to the x the call itself showed one tap earlier.
+@pytest.mark.parametrize("D,B,m,n,variant", FORWARD_CASES)
+def test_forward_forms(gpu_device, D, B, m, n, variant):
+    """One stage of og_forward: EVERY projection and message-MLP launch, in launch order, against the restatement (tests/proj_plan_ref.py), then x after
+    the self layer and after the cross layer against float64 of that layer applied to the x the call itself showed one tap earlier.
       d128 m128 n4100 (T0 = 256, T = 8456): the stream launch of the self layer, the stream launch with a row split, proj_small for the k | v of
                          the updated image 0, mlp_fused<128> for the self layer and side 1, mlp_small<128> for side 0
       d128 m130 n4100 (T0 = 260): no row split -- a stream launch at row offset T0 and proj_small for image 0's q
       d256 m128 n160 / m130 n97: one proj_small launch with a row split / three proj_small launches in the cross layer
-      d256 m128 n4100: mlp_fused<256> under the forward (scales_dev set); its big projections are GEMMs
+      d256 m128 n4100: mlp_fused<256> under the forward (scales_dev set); the self launch and image 1's q | k | v (8200 rows) are 128-tile GEMMs
+      d256 B12 m1024 n1024 (T0 = 12288): 2304 units -> proj_wstat_kernel for the self layer; the cross launch has 1536 units (below the 2048-unit
+                         floor) and exactly 192 big tiles -> the row-split big2 GEMM; the k | v has 768 units and 96 big tiles -> the 128-token tile GEMM
+      d256 B16 m1024 n1024 (T0 = 16384): the cross launch counts T0 / 32 + ceil(T1 / 32) * 3 = 512 + 1536 = 2048 units -> ONE proj_wstat launch with the row split
+      d128 favor_relu (one head, QW = 5 D): no fragment-major copy exists, every projection is a tile GEMM; a range that spans the feature and value
+                         blocks is TWO launches (ReLU / none), image 0's q in the cross layer one
       prescales: the multipliers {1 / S_qkv, 1 / S_0, 1 / S_3} of both layers are pairwise different (asserted from the packed blob)"""
     from tests.packed_model import layout_of
-    cfg, sd, model = _model(D, _distinct_prescales if prescales else None)
+    prescales, favor = variant == "prescales", variant == "favor"
+    H, att = (1, "favor_relu") if favor else (4, "softmax")
+    cfg, sd, model = _model(D, _distinct_prescales if prescales else None, heads=H, attention=att, iters=2 if B < 12 and not favor else 3)
     if prescales:
         L, blob = layout_of(model), model.pack_host()
         for l in (0, 1):
@@ -642,12 +627,42 @@ def test_forward_forms(gpu_device, D, B, m, n, prescales):
     dd = to_device(data, _dev())
     taps = [tuple(t.cpu() for t in model.forward_tap(dd, k)) for k in (0, 1)]
     box = []
-    inst = _traced(lambda: box.append(model.forward_tap(dd, 2)))
+    inst = _gnn_launches(lambda: box.append(model.forward_tap(dd, 2)), D)
     taps.append(tuple(t.cpu() for t in box[0]))
-    want = expected_forward(D, B, m, n)
-    assert Counter(inst) == want, (Counter(inst), want)
+    want = forward_sequence(D, B, m, n, favor=favor)
+    assert inst == want, (inst, want)
+    tag = f"forward D={D} B={B} m={m} n={n}{' ' + variant if variant else ''}"
     for l in (0, 1):
-        r0, r1 = _layer64(sd, 4, l, taps[l][0].double(), taps[l][1].double())
+        r0, r1 = _layer64(sd, H, l, taps[l][0].double(), taps[l][1].double(), att)
         scale = max(1.0, r0.abs().max().item(), r1.abs().max().item())
-        _check(f"forward D={D} B={B} m={m} n={n}{' prescales' if prescales else ''} layer {l} image 0", taps[l + 1][0], r0, TOL_TAP * scale)
-        _check(f"forward D={D} B={B} m={m} n={n}{' prescales' if prescales else ''} layer {l} image 1", taps[l + 1][1], r1, TOL_TAP * scale)
+        _check(f"{tag} layer {l} image 0", taps[l + 1][0], r0, TOL_TAP * scale)
+        _check(f"{tag} layer {l} image 1", taps[l + 1][1], r1, TOL_TAP * scale)
+
+
+@gpu
+def test_forward_forms_ragged_batch(gpu_device):
+    """og_forward_ragged at 256-d, 8 pairs, T0 = 512 and T1 = 22016 token rows: as a uniform batch these counts would put the self launch (2112 units)
+    and the cross launch (2080 units, 260 big tiles, T0 and T whole tiles) on proj_wstat_kernel with a row split (asserted from the restatement); a
+    ragged batch takes neither the weight-stationary kernel nor a row-split launch -- big2 GEMMs, and image 0's q as a launch of its own.
+    og_forward_tap has no ragged form: every pair's scores against the same pair's own call (tests/test_gpu_parity.py: test_ragged_packed_wide_range)."""
+    D = 256
+    cfg, sd, model = _model(D, iters=3)
+    cpu = []
+    for i, (m, n) in enumerate(zip(*RAGGED_LENS)):
+        p = syn.make_pair(m, n, D, 1, seed=900 + i)
+        p["image0_size"] = list(syn.IMAGE_WH); p["image1_size"] = list(syn.IMAGE_WH)
+        cpu.append(p)
+    pairs = [to_device(p, _dev()) for p in cpu]
+    box = []
+    inst = _gnn_launches(lambda: box.append(model.match_ragged(pairs, 0.2)), D)
+    want = forward_sequence(D, len(cpu), 0, 0, lens=RAGGED_LENS)
+    assert inst == want, (inst, want)
+    assert "proj_wstat_kernel" not in inst and inst.count("gemm_nt_f16x3_big2_kernel<2, 1>") == 2
+    assert forward_sequence(D, 1, sum(RAGGED_LENS[0]), sum(RAGGED_LENS[1])).count("proj_wstat_kernel") == 2
+    for p, r, m, n in zip(pairs, box[0], *RAGGED_LENS):
+        one = {k: (v[None] if torch.is_tensor(v) else v) for k, v in p.items()}
+        ref = model.match(one, 0.2)
+        assert r["scores"].shape == (m + 1, n + 1)
+        err = (r["scores"] - ref["scores"][0]).abs().max().item()
+        print(f"[proj/mlp forms] ragged pair {m}x{n}: scores against its own call, err {err:.2e}")
+        assert err < 1e-4, (m, n, err)
