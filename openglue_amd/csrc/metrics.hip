@@ -79,6 +79,21 @@ __host__ __device__ inline void cmul_acc(const Quad& q, const Lin& l, double s, 
                 out[mono(ex(i) + ex(j) + ex(k), ey(i) + ey(j) + ey(k), ez(i) + ez(j) + ez(k))] += s * q.c[qidx(i, j)] * l.c[k];
 }
 
+// The elimination below pivots in columns 0..4 and fixes the coefficient of W at 1, which singles out entries of E: with the
+// translation along camera 1's optical axis the third row of E = [T]x R is zero, the solution lies at infinity of that chart and
+// is lost; with R = I as well, columns 1 and 3 of the constraints coincide and a pivot is rounding noise.  So the solver works in
+// coordinates reflected by a fixed Householder matrix H = I - 2 v v^T / |v|^2 with nine generic entries: the constraint rows
+// before the elimination, the null-space basis after Gram-Schmidt (H is a symmetric involution).  No entry of E is special then.
+__host__ __device__ inline void reflect9(double (&r)[9]) {
+    constexpr double v[9] = {0.31, -0.27, 0.35, 0.29, -0.33, 0.26, -0.34, 0.28, 0.32};
+    double vv = 0.0, d = 0.0;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) { vv += v[c] * v[c]; d += r[c] * v[c]; }
+    const double f = 2.0 * d / vv;
+#pragma unroll
+    for (int c = 0; c < 9; ++c) r[c] -= f * v[c];
+}
+
 // Stage 1 of the solver for one problem.  x0, x1: 5 calibrated points each ([5][2]).  A: the 10 x 20 elimination matrix,
 // element (r, c) at A[(r * 20 + c) * S].  inter: 76 doubles at stride IS (basis X Y Z W [4][9], then the coefficients of
 // the three rows of B(z) = [[kx ky k1] [lx ly l1] [mx my m1]] (x / y: 4 ascending in z, 1: 5), then 1.0 if the problem is sound).
@@ -91,6 +106,7 @@ __host__ __device__ inline void essential_poly(const double* x0, const double* x
         Q[r][0] = u1 * u0; Q[r][1] = u1 * v0; Q[r][2] = u1;
         Q[r][3] = v1 * u0; Q[r][4] = v1 * v0; Q[r][5] = v1;
         Q[r][6] = u0;      Q[r][7] = v0;      Q[r][8] = 1.0;
+        reflect9(Q[r]);
     }
     bool ok = true;
 #pragma unroll
@@ -144,6 +160,8 @@ __host__ __device__ inline void essential_poly(const double* x0, const double* x
 #pragma unroll
         for (int c = 0; c < 9; ++c) Nb[f][c] *= inv;
     }
+#pragma unroll
+    for (int f = 0; f < 4; ++f) reflect9(Nb[f]);      // back to the entries of E; H is orthogonal, the basis stays orthonormal
 #pragma unroll
     for (int f = 0; f < 4; ++f)
 #pragma unroll
@@ -259,8 +277,13 @@ __host__ __device__ inline void constraints(const double (&E)[9], double (&r)[10
     r[9] = E[0] * (E[4] * E[8] - E[5] * E[7]) - E[1] * (E[3] * E[8] - E[5] * E[6]) + E[2] * (E[3] * E[7] - E[4] * E[6]);
 }
 
-// Up to three Gauss-Newton steps on (x, y, z) against the ten constraints (forward-difference Jacobian), each kept only if it lowers
-// the residual: the roots of the eliminated polynomial carry the rounding of the elimination, this takes it back out.
+// Up to kPolishSteps Gauss-Newton steps on (x, y, z) against the ten constraints (forward-difference Jacobian), each kept only if it
+// lowers the residual: the roots of the eliminated polynomial carry the rounding of the elimination, this takes it back out.  A
+// root ends the loop at its first step that does not improve, which for a well-conditioned elimination is the second or third.
+// Where the leading 10 x 10 block is badly conditioned in this chart (about 1 problem in 600) the root of the eliminated
+// polynomial can be 0.02 off in z; Gauss-Newton then contracts by only ~5x a step before it turns quadratic and needs ten steps to
+// reach the 1e-9 keep rule (three left it at 6e-5 and the true solution was dropped).
+constexpr int kPolishSteps = 12;
 __host__ __device__ inline void polish(const double (&basis)[36], double& x, double& y, double& z) {
     auto build = [&](double a, double b, double c, double (&E)[9]) {
 #pragma unroll
@@ -271,7 +294,7 @@ __host__ __device__ inline void polish(const double (&basis)[36], double& x, dou
         for (int k = 0; k < 10; ++k) t += r[k] * r[k];
         return t; };
 #pragma unroll 1
-    for (int it = 0; it < 3; ++it) {
+    for (int it = 0; it < kPolishSteps; ++it) {
         double E[9], r0[10], J[3][10];
         build(x, y, z, E);
         constraints(E, r0);
@@ -608,10 +631,10 @@ __device__ __forceinline__ bool sampson_inlier(const float (&e)[9], float4 q, fl
 
 constexpr int kScoreChunk = 1024;
 
-__global__ void __launch_bounds__(256) score_kernel(PoseWs w, int m, int H) {
+__global__ void __launch_bounds__(256) score_kernel(PoseWs w, int m, int H, int groups) {
     __shared__ float4 pts[kScoreChunk];
-    const int b = blockIdx.y;
-    const int model = blockIdx.x * 256 + threadIdx.x;        // h * 10 + s
+    const int b = blockIdx.x / groups;                       // `groups` workgroups per pair, pair-major along x
+    const int model = (blockIdx.x - b * groups) * 256 + threadIdx.x;        // h * 10 + s
     const int h = model / kMaxSol, s = model - h * kMaxSol;
     const int64_t prob = (int64_t)b * H + h;
     const bool live = h < H && s < w.nsol[prob];
@@ -825,7 +848,8 @@ extern "C" int og_relative_pose(int32_t batch, int32_t m, int32_t n, const float
     hipLaunchKernelGGL(prep_kernel, dim3(batch), dim3(256), 0, st, g, ransac_threshold, w);
     hipLaunchKernelGGL(solve_poly_kernel, dim3((count + kPolyLds - 1) / kPolyLds), dim3(kPolyLds), 0, st, src, count, w.E);
     hipLaunchKernelGGL(solve_roots_kernel, dim3((count + 255) / 256), dim3(256), 0, st, count, w.E, w.nsol);
-    hipLaunchKernelGGL(score_kernel, dim3((hypotheses * kMaxSol + 255) / 256, batch), dim3(256), 0, st, w, m, hypotheses);
+    const int groups = (hypotheses * kMaxSol + 255) / 256;
+    hipLaunchKernelGGL(score_kernel, dim3(batch * groups), dim3(256), 0, st, w, m, hypotheses, groups);
     hipLaunchKernelGGL(finish_kernel, dim3(batch), dim3(256), 0, st, g, w, hypotheses, error, R_pred, t_pred, inliers, num_inliers);
     return og_launch_status();
 }
