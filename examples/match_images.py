@@ -4,6 +4,10 @@ The pair is related by a homography, which is degenerate for a fundamental matri
 count is shown, the accuracy of the stage is the business of tests/test_gpu_geometry.py.
 
     python examples/match_images.py [--size 480x640] [--keypoints 2048] [--match-threshold 0.2] [--features {superpoint,sift,dog_affnet_hardnet}]
+                                    [--verify {fundamental,homography}]
+
+--verify homography runs find_homography (cv2.findHomography(..., cv2.RANSAC, 3.0)) as the last stage instead, the model that fits
+this planar pair, and prints its inliers and the mean corner error against the homography the pair was made with.
 
 --features sift runs the reference's 128-d pipeline: the SIFT extractor (openglue_amd/sift.py) and a 128-d SuperGlue.
 --features dog_affnet_hardnet runs DoG + AffNet + OriNet + HardNet (openglue_amd/affnet_hardnet.py, seeded weights) with the affine
@@ -23,7 +27,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from examples.openglue_matcher import OpenGlueMatcher  # noqa: E402
 from openglue_amd import synthetic as syn  # noqa: E402
 from openglue_amd.affnet_hardnet import DoGAffNetHardNet  # noqa: E402
-from openglue_amd.geometry import find_fundamental  # noqa: E402
+from openglue_amd.geometry import find_fundamental, find_homography  # noqa: E402
+from openglue_amd.metrics import homography_error  # noqa: E402
 from openglue_amd.sift import SIFT  # noqa: E402
 from openglue_amd.superglue import SuperGlue  # noqa: E402
 from openglue_amd.superpoint import SuperPointNetBn  # noqa: E402
@@ -35,11 +40,14 @@ def main():
     ap.add_argument("--keypoints", type=int, default=2048)
     ap.add_argument("--match-threshold", type=float, default=0.2)
     ap.add_argument("--features", choices=("superpoint", "sift", "dog_affnet_hardnet"), default="superpoint")
+    ap.add_argument("--verify", choices=("fundamental", "homography"), default="fundamental")
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split("x"))
     dev = torch.device("cuda:0")
     img0 = syn.make_image(H, W, seed=1)
-    img1 = syn.warp_image(img0, syn.random_homography(H, W, seed=2))
+    Hm = syn.random_homography(H, W, seed=2)
+    img1 = syn.warp_image(img0, Hm)
+    verify = find_homography if a.verify == "homography" else find_fundamental
     affine = a.features == "dog_affnet_hardnet"
     if a.features == "sift":
         sp = SIFT(max_keypoints=a.keypoints).to(dev)
@@ -62,7 +70,7 @@ def main():
     data = {"image0": img0.to(dev), "image1": img1.to(dev)}
     for _ in range(2):                      # warm-up: packing, allocator
         out = matcher(data)
-        find_fundamental(out["keypoints0"], out["keypoints1"])
+        verify(out["keypoints0"], out["keypoints1"])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     lafs, _, _ = sp(torch.cat([data["image0"], data["image1"]]))
@@ -71,12 +79,16 @@ def main():
     out = matcher(data)
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    F, inliers = find_fundamental(out["keypoints0"], out["keypoints1"])      # cv2.findFundamentalMat(..., USAC_MAGSAC, 1.0, 0.999, 100000)
+    F, inliers = verify(out["keypoints0"], out["keypoints1"])      # cv2.findFundamentalMat(..., USAC_MAGSAC, 1.0, 0.999, 100000) / cv2.findHomography
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     print(f"{H}x{W}: {lafs.shape[1]} keypoints per image, {out['keypoints0'].shape[0]} matches")
     print(f"{ {'sift': 'SIFT', 'superpoint': 'SuperPoint', 'dog_affnet_hardnet': 'DoG + AffNet + OriNet + HardNet'}[a.features]} on both images {1e3 * (t1 - t0):.2f} ms; images -> matches {1e3 * (t2 - t1):.2f} ms")
-    print(f"fundamental matrix: {int(inliers.sum())} inliers of {inliers.shape[0]} matches, {1e3 * (t3 - t2):.2f} ms")
+    if a.verify == "homography":
+        err = float(homography_error(F[None], torch.as_tensor(Hm, dtype=torch.float32, device=dev).reshape(1, 3, 3), (W, H))[0])
+        print(f"homography: {int(inliers.sum())} inliers of {inliers.shape[0]} matches, mean corner error {err:.2f} px, {1e3 * (t3 - t2):.2f} ms")
+    else:
+        print(f"fundamental matrix: {int(inliers.sum())} inliers of {inliers.shape[0]} matches, {1e3 * (t3 - t2):.2f} ms")
 
 
 if __name__ == "__main__":

@@ -13,8 +13,13 @@ decoding and resizing.  From there to the parameter update every tensor stays on
 frames and the optimizer step except the extractor's own keypoint count (one integer per image batch) and the numbers printed here.
 A fresh pair is synthesised from the same frames every step, as a data loader would.
 
+--validate adds what the reference's stage lacks (its data module has a train_dataloader only and it trains with
+num_sanity_val_steps=0): after the last step the model goes to eval(), fresh pairs from the same frames go through the extractor and
+SuperGlue.match, and metrics.HomographyAccuracy / metrics.HomographyAUC judge the matches against the pairs' own H: precision and
+matching score at 3 px, and the AUC of the mean corner error of a homography estimated from the matches (geometry.homography).
+
     python examples/pretrain_homography.py [--steps 5] [--pairs 2] [--size 240 320] [--offset 24] [--features sift|superpoint]
-                                         [--augment none|weak_color_aug]"""
+                                         [--augment none|weak_color_aug] [--validate]"""
 import argparse
 import os
 import sys
@@ -24,7 +29,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from examples.train_fit import GAMMA, LR, MAX_GRAD_NORM                # noqa: E402
 from examples.train_step import MARGIN, training_step                  # noqa: E402
-from openglue_amd import augment, optim, pairs, synthetic as syn       # noqa: E402
+from openglue_amd import augment, features, metrics, optim, pairs, synthetic as syn       # noqa: E402
 from openglue_amd.sift import SIFT                                     # noqa: E402
 from openglue_amd.superglue import SuperGlue                           # noqa: E402
 from openglue_amd.superpoint import SuperPointNetBn                    # noqa: E402
@@ -55,7 +60,40 @@ def extract(extractor, item):
     return batch
 
 
-def run(steps=5, n_pairs=2, size=(240, 320), offset=24, feature="sift", keypoints=512, stages=3, seed=0, log=print, augmentation="none"):
+VAL_THRESHOLD = 3.0                 # pixels: a correct match, and the RANSAC inlier threshold
+VAL_AUC_THRESHOLDS = (3, 5, 10)     # pixels of mean corner error
+
+
+def validate(model, extractor, frames, offset, gen, batches=2, match_threshold=0.2, log=print):
+    """`batches` fresh pair batches through eval() -> SuperGlue.match -> HomographyAccuracy and HomographyAUC.  Leaves the model in
+    eval().  -> {'Precision', 'Matching Score', 'AUC@3px', 'AUC@5px', 'AUC@10px'} as floats"""
+    model.eval()
+    h, w = frames.shape[1] - 2 * offset, frames.shape[2] - 2 * offset
+    acc = metrics.HomographyAccuracy(VAL_THRESHOLD)
+    auc = metrics.HomographyAUC(VAL_AUC_THRESHOLDS, VAL_THRESHOLD, (w, h))
+    with torch.no_grad():
+        for _ in range(batches):
+            batch = extract(extractor, pairs.homography_pairs(frames, offset, generator=gen))
+            if batch["lafs0"].shape[1] == 0 or batch["lafs1"].shape[1] == 0:
+                continue
+            f = [features.prepare_features_output(batch["lafs" + s], batch["scores" + s], batch["descriptors" + s], "none") for s in "01"]
+            data = {"image0_size": batch["image0_size"], "image1_size": batch["image1_size"]}
+            for s in "01":
+                data.update({"keypoints" + s: f[int(s)]["keypoints"], "local_descriptors" + s: f[int(s)]["local_descriptors"],
+                             "side_info" + s: f[int(s)]["side_info"]})
+            out = model.match(data, match_threshold, both_sides=False)
+            acc.update_batch(data["keypoints0"], data["keypoints1"], out["matches0"], batch["transformation"])
+            auc.update_batch(data["keypoints0"], data["keypoints1"], out["matches0"], batch["transformation"])
+    if not acc.precision:
+        log("validation: no keypoints, nothing to judge")
+        return {}
+    result = {k: float(v) for k, v in {**acc.compute(), **auc.compute()}.items()}
+    log("validation  " + "  ".join(f"{k} {v:.4f}" for k, v in result.items()))
+    return result
+
+
+def run(steps=5, n_pairs=2, size=(240, 320), offset=24, feature="sift", keypoints=512, stages=3, seed=0, log=print, augmentation="none",
+        validation=False):
     """-> [(matched labels, total loss)] per step"""
     dev = torch.device("cuda:0")
     H, W = size
@@ -85,6 +123,8 @@ def run(steps=5, n_pairs=2, size=(240, 320), offset=24, feature="sift", keypoint
         history.append((matched, float(total.detach())))
         log(f"step {s:2d}  keypoints {batch['lafs0'].shape[1]} / {batch['lafs1'].shape[1]} per image  matched labels {matched}  "
             f"loss {history[-1][1]:.4f}  nll {float(lo['loss']):.4f}  metric {float(lo['metric_loss']):.4f}")
+    if validation:
+        validate(model, extractor, frames, offset, gen, log=log)
     return history
 
 
@@ -97,5 +137,6 @@ if __name__ == "__main__":
     ap.add_argument("--features", default="sift", choices=("sift", "superpoint"))
     ap.add_argument("--keypoints", type=int, default=512)
     ap.add_argument("--augment", default="none", choices=("none", "weak_color_aug"))
+    ap.add_argument("--validate", action="store_true", help="after training: precision, matching score and corner-error AUC on fresh pairs")
     a = ap.parse_args()
-    run(a.steps, a.pairs, tuple(a.size), a.offset, a.features, a.keypoints, augmentation=a.augment)
+    run(a.steps, a.pairs, tuple(a.size), a.offset, a.features, a.keypoints, augmentation=a.augment, validation=a.validate)

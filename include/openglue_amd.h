@@ -587,6 +587,44 @@ int og_fundamental_matrix(int32_t batch, int32_t m, int32_t n, const float* keyp
                           int32_t refine, uint64_t seed, int64_t pair_offset, double* F, uint8_t* inliers,
                           int32_t* num_inliers, int32_t* best_model, void* workspace_dev, void* stream);
 
+/* Planar geometric verification and the validation metrics of the homography pre-training stage (csrc/homography.hip): what a user
+ * takes from cv2.findHomography, and the perspective counterparts of og_epipolar_precision and og_relative_pose's error.  Added to
+ * ABI v14 without a version bump: five new entries, nothing existing changes.  Pairs in the layout of the metrics above; x1 ~ H x0
+ * with x0 from keypoints0, H row-major.
+ *
+ * og_homography_4pt: the four-point minimal solver, fp64.  x0, x1 [count][4][2] correspondences with coordinates of order 1 (e.g.
+ *   Hartley-normalised) -> H [count][9] (unit Frobenius norm, largest-magnitude entry positive; zero when num_solutions[p] is 0) and
+ *   num_solutions [count] int32 (0 or 1).  A model is kept when each of the four point triples has a signed area above 1e-9 in both
+ *   images with the same sign in both (cv2's orientation test, which removes collinear triples too), all nine entries are finite and
+ *   the eight DLT constraints hold to 1e-9.  One kernel, no workspace.  OG_E_INVALID for count <= 0 or count > 2^30.
+ * og_homography: per pair, Hartley normalisation of the valid matches (fp64, as og_fundamental_matrix), `hypotheses` samples of 4
+ *   distinct matches drawn by the counter-based hash of (seed, pair_offset + b, hypothesis), every model scored by the squared forward
+ *   transfer error |proj(H, x0) - x1|^2 in pixels^2 <= threshold^2 (fp32; a non-finite error is an outlier); most inliers win, the
+ *   lowest hypothesis on ties.  Then `refine` rounds (0: none) of a normalised DLT least-squares fit to the current inliers, each kept
+ *   if it is finite and has no fewer inliers, skipped below 5 inliers.  H [B][3][3] fp64 in pixels, unit Frobenius norm, largest
+ *   entry positive; inliers [B][m] uint8 at the positions of keypoints0; num_inliers [B]; best_model [B] = hypothesis of the RANSAC
+ *   winner.  With fewer than 4 valid matches or no model: H = 0, no inliers, best_model = -1.  workspace:
+ *   og_homography_workspace_bytes, 16-byte aligned (OG_E_ALIGN).  OG_E_INVALID for hypotheses <= 0, batch hypotheses > 2^30 (the
+ *   workspace size is then 0), refine < 0 or a negative or NaN threshold.  Four kernels, no host synchronisation, bit-identical from
+ *   run to run.
+ * og_homography_precision: H_true [B][3][3] fp32.  For every valid match |proj(H_true, keypoints0[i]) - keypoints1[matches0[i]]| in
+ *   fp64; a match is correct when it is < threshold (pixels).  precision = correct / matched, matching_score = correct /
+ *   num_keypoints0 (both 0 without matches), num_correct [B].  One kernel.
+ * og_homography_corner_error: error [B] fp32 = the mean distance in pixels between the four corners (0, 0), (0, height - 1),
+ *   (width - 1, 0), (width - 1, height - 1) mapped by H_est [B][3][3] fp64 and by H_true [B][3][3] fp32, in fp64; +inf for an
+ *   all-zero estimate or a non-finite projection.  One kernel.  OG_E_INVALID for width or height <= 0. */
+int og_homography_4pt(int32_t count, const double* x0, const double* x1, double* H, int32_t* num_solutions, void* stream);
+size_t og_homography_workspace_bytes(int32_t batch, int32_t m, int32_t hypotheses);
+int og_homography(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1, const int64_t* matches0,
+                  const int32_t* num_keypoints0, float threshold, int32_t hypotheses, int32_t refine, uint64_t seed,
+                  int64_t pair_offset, double* H, uint8_t* inliers, int32_t* num_inliers, int32_t* best_model, void* workspace_dev,
+                  void* stream);
+int og_homography_precision(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                            const int64_t* matches0, const int32_t* num_keypoints0, const float* H_true, float threshold,
+                            float* precision, float* matching_score, int32_t* num_correct, void* stream);
+int og_homography_corner_error(int32_t batch, const double* H_est, const float* H_true, int32_t width, int32_t height, float* error,
+                               void* stream);
+
 /* ABI v13 -- the SuperPoint detector / descriptor (models/features/superpoint/model.py, SuperPointNet / SuperPointNetBn), inference
  * only (eval-mode BatchNorm, folded at pack time).  descriptor_dim 256.  Image [B][H][W] fp32, H, W >= 8, B * H * W <= 2^26;
  * Hc = H / 8, Wc = W / 8 (floor, as the three 2x2 max-pools), the heatmap is [B][8 Hc][8 Wc].

@@ -20,6 +20,23 @@ Where this deliberately differs from cv2.USAC_MAGSAC:
   * there is no degeneracy test for planar scenes or dominant planes: for such input F is whatever the data support (a homography
     leaves a family of F that fit equally well), and the mask is still finite and deterministic.
 With fewer than 7 valid matches, or no surviving model, F is zero, no match is an inlier and best_model is -1 (cv2 returns None).
+
+Planar scenes, and the pairs of the homography pre-training stage, get the same treatment with the homography as the model
+(cv2.findHomography(keypoints0, keypoints1, cv2.RANSAC, 3.0)):
+
+  homography           a whole SuperGlue.match batch -> H, inlier mask, counts
+  find_homography      one pair of compacted matches -> (H / H[2, 2], inliers), cv2's return order
+  homography_4pt       the four-point minimal solver on its own
+
+over og_homography / og_homography_4pt (csrc/homography.hip).  Per pair: the same normalisation and draws with 4 matches per sample,
+at most one model per sample, scored by its number of matches with squared forward transfer error |proj(H, x0) - x1|^2 <=
+threshold^2 (pixels), the winner by most inliers and the lowest hypothesis on ties, then `refine` normalised DLT refits on the
+inliers, each kept if it loses no inlier.  Where this deliberately differs from cv2.findHomography(..., cv2.RANSAC):
+  * the sample count is fixed and the draws are the hash's, as above (2048 samples of 4 give 0.999 confidence down to an inlier
+    ratio of about 0.25);
+  * a sample is rejected by cv2's orientation test on its four point triples, which here also rejects a collinear triple;
+  * the refits are linear least squares (DLT) on the inliers; there is no Levenberg-Marquardt polish of the reprojection error.
+With fewer than 4 valid matches, or no surviving model, H is zero, no match is an inlier and best_model is -1.
 """
 from __future__ import annotations
 
@@ -100,3 +117,70 @@ def fundamental_7pt(x0: torch.Tensor, x1: torch.Tensor):
     ns = torch.empty(count, device=dev, dtype=torch.int32)
     _lib.call("og_fundamental_7pt", dev, count, a.data_ptr(), b.data_ptr(), F.data_ptr(), ns.data_ptr(), _lib.STREAM)
     return F, ns
+
+
+def homography(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold: float = 3.0, hypotheses: int = 2048,
+               refine: int = 2, seed: int = 0, pair_offset: int = 0) -> Dict[str, torch.Tensor]:
+    """keypoints0 [B, M, 2], keypoints1 [B, N, 2] (pixels), matches0 [B, M] (-1 or outside [0, N): no match), num_keypoints0 [B]
+    (None: M) -> {'H' [B, 3, 3] float64 in pixels with x1 ~ H x0, unit Frobenius norm, largest entry positive; 'inliers' [B, M]
+    bool at the positions of keypoints0; 'num_inliers' [B] int32; 'best_model' [B] int32 = hypothesis of the RANSAC winner, -1
+    without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is)."""
+    s0, s1, sm = _shape(keypoints0, "keypoints0"), _shape(keypoints1, "keypoints1"), _shape(matches0, "matches0")
+    if len(s0) != 3 or s0[2] != 2 or len(s1) != 3 or s1[2] != 2 or s1[0] != s0[0] or s0[0] == 0:
+        raise ValueError(f"keypoints0 / keypoints1 must be [B, M, 2] / [B, N, 2] with B > 0, got {list(s0)} / {list(s1)}")
+    B, M, N = s0[0], s0[1], s1[1]
+    if sm != (B, M):
+        raise ValueError(f"matches0 must be [B, M] = [{B}, {M}], got {list(sm)}")
+    if num_keypoints0 is not None and _shape(num_keypoints0, "num_keypoints0") != (B,):
+        raise ValueError(f"num_keypoints0 must be [B] = [{B}], got {list(num_keypoints0.shape)}")
+    hypotheses, refine = int(hypotheses), int(refine)
+    if hypotheses <= 0 or refine < 0 or not float(threshold) >= 0.0:
+        raise ValueError(f"hypotheses must be positive, refine and threshold non-negative, got {hypotheses}, {refine}, {threshold}")
+    if B * hypotheses > 2 ** 30:
+        raise ValueError(f"batch * hypotheses must not exceed 2^30, got {B} * {hypotheses}")
+    k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
+    k1 = _lib.gpu_tensor(keypoints1, "keypoints1", convert=True)
+    m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
+    nk = None if num_keypoints0 is None else _lib.gpu_tensor(num_keypoints0, "num_keypoints0", torch.int32, convert=True)
+    dev = k0.device
+    ws, wp = _lib.workspace(_lib.load().og_homography_workspace_bytes(B, M, hypotheses), dev)      # sizes checked above
+    H = torch.empty(B, 3, 3, device=dev, dtype=torch.float64)
+    inl = torch.empty(B, max(M, 1), device=dev, dtype=torch.uint8)
+    ninl = torch.empty(B, device=dev, dtype=torch.int32)
+    best = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.call("og_homography", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
+              hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), H.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
+              best.data_ptr(), wp, _lib.STREAM)
+    return {"H": H, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best}
+
+
+def find_homography(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One pair as a caller passes it to cv2.findHomography: matched keypoints [K, 2] of both images -> (H [3, 3] float64 divided by
+    H[2, 2] as cv2 returns it, zero without a model; inliers [K] bool).  Keyword arguments as homography (threshold, hypotheses,
+    refine, seed, pair_offset).  An H whose last entry is 0 (the origin sent to infinity) has no such form and comes out non-finite."""
+    s0, s1 = _shape(matched_kpts0, "matched_kpts0"), _shape(matched_kpts1, "matched_kpts1")
+    if len(s0) != 2 or s0[1] != 2 or s1 != s0:
+        raise ValueError(f"matched_kpts0 / matched_kpts1 must both be [K, 2], got {list(s0)} / {list(s1)}")
+    k0 = _lib.gpu_tensor(matched_kpts0, "matched_kpts0", convert=True)
+    k1 = _lib.gpu_tensor(matched_kpts1, "matched_kpts1", convert=True)
+    m0 = torch.arange(k0.shape[0], device=k0.device).unsqueeze(0)
+    r = homography(k0.unsqueeze(0), k1.unsqueeze(0), m0, **kw)
+    H = r["H"][0]
+    return torch.where(r["best_model"][0] >= 0, H / H[2, 2], torch.zeros_like(H)), r["inliers"][0]      # no host synchronisation
+
+
+def homography_4pt(x0: torch.Tensor, x1: torch.Tensor):
+    """The four-point minimal solver on its own: x0, x1 [count, 4, 2] correspondences (x1 ~ H x0) with coordinates of order 1
+    -> (H [count, 3, 3] float64, unit Frobenius norm, largest entry positive, zero without a solution; num_solutions [count] int32,
+    0 or 1)."""
+    s0, s1 = _shape(x0, "x0"), _shape(x1, "x1")
+    if len(s0) != 3 or s0[1:] != (4, 2) or s1 != s0 or not 0 < s0[0] <= 2 ** 30:
+        raise ValueError(f"x0 / x1 must both be [count, 4, 2] with 0 < count <= 2^30, got {list(s0)} / {list(s1)}")
+    a = _lib.gpu_tensor(x0, "x0", torch.float64, convert=True)
+    b = _lib.gpu_tensor(x1, "x1", torch.float64, convert=True)
+    count = a.shape[0]
+    dev = a.device
+    H = torch.empty(count, 3, 3, device=dev, dtype=torch.float64)
+    ns = torch.empty(count, device=dev, dtype=torch.int32)
+    _lib.call("og_homography_4pt", dev, count, a.data_ptr(), b.data_ptr(), H.data_ptr(), ns.data_ptr(), _lib.STREAM)
+    return H, ns

@@ -20,6 +20,15 @@ Where the pose estimate deliberately differs from the reference's cv2.findEssent
     triangulation (the same sign except for points at near-infinite depth);
   * the cosines of the rotation and translation errors are clamped to [-1, 1] (the reference's translation cosine is not,
     so there a value that rounds above 1 gives NaN).
+
+The homography pre-training stage has no validation in the reference (OxfordParis1MDataModule has a train_dataloader only, and
+pretrain_homography.py runs with num_sanity_val_steps=0).  Its items carry transformation['H'] instead of K0, K1, R, T, so the two
+classes above cannot judge them; their perspective counterparts, over og_homography_precision / og_homography_corner_error
+(csrc/homography.hip) and geometry.homography, can:
+
+  HomographyAccuracy          precision and matching score from the transfer distance under the true H (pixels)
+  HomographyAUC               a homography per pair by RANSAC, its mean corner error, AUC at the given thresholds (pixels)
+  homography_precision, homography_error   their functional forms
 """
 from __future__ import annotations
 
@@ -27,7 +36,7 @@ from typing import Dict, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, geometry
 
 _TKEYS = ("K0", "K1", "R", "T")
 
@@ -117,6 +126,13 @@ def essential_5pt(x0: torch.Tensor, x1: torch.Tensor):
 def _single_pair(matched_kpts0, matched_kpts1, transformation, num_detected_kpts=None):
     """One pair as the reference passes it (compacted matches, a per-pair transformation) -> a B = 1 batch.  With
     num_detected_kpts the keypoints are padded to that many rows with -1 matches, so that matching_score divides by it."""
+    kp0, kp1, m0, nk = _pad_pair(matched_kpts0, matched_kpts1, num_detected_kpts)
+    tr = {key: _lib.gpu_tensor(transformation[key], f"transformation['{key}']", convert=True).unsqueeze(0) for key in _TKEYS}
+    return kp0, kp1, m0, tr, nk
+
+
+def _pad_pair(matched_kpts0, matched_kpts1, num_detected_kpts=None):
+    """The keypoints and matches of _single_pair: (keypoints0 [1, M, 2], keypoints1 [1, K, 2], matches0 [1, M], num_keypoints0)."""
     k0 = _lib.gpu_tensor(matched_kpts0, "matched_kpts0", convert=True)
     k1 = _lib.gpu_tensor(matched_kpts1, "matched_kpts1", convert=True)
     if k0.dim() != 2 or k0.shape[1] != 2 or tuple(k1.shape) != tuple(k0.shape):
@@ -128,9 +144,8 @@ def _single_pair(matched_kpts0, matched_kpts1, transformation, num_detected_kpts
     kp0[0, :K] = k0
     m0 = torch.full((1, M), -1, device=dev, dtype=torch.int64)
     m0[0, :K] = torch.arange(K, device=dev)
-    tr = {key: _lib.gpu_tensor(transformation[key], f"transformation['{key}']", convert=True).unsqueeze(0) for key in _TKEYS}
     nk = None if num_detected_kpts is None else torch.full((1,), int(num_detected_kpts), device=dev, dtype=torch.int32)
-    return kp0, k1.unsqueeze(0), m0, tr, nk
+    return kp0, k1.unsqueeze(0), m0, nk
 
 
 class AccuracyUsingEpipolarDist:
@@ -194,6 +209,129 @@ class CameraPoseAUC:
 
     def compute(self):
         return pose_auc(torch.cat(self.pose_errors), self.auc_thresholds)
+
+
+def _true_h(transformation, B: int) -> torch.Tensor:
+    """transformation['H'] of a perspective item (pairs.homography_pairs: float32, image0 -> image1 in pixels) -> [B, 3, 3]"""
+    s = geometry._shape(transformation["H"], "transformation['H']")
+    if s != (B, 3, 3):
+        raise ValueError(f"transformation['H'] must be {[B, 3, 3]}, got {list(s)}")
+    return _lib.gpu_tensor(transformation["H"], "transformation['H']", convert=True)
+
+
+def homography_precision(keypoints0, keypoints1, matches0, transformation, num_keypoints0=None, threshold: float = 3.0
+                         ) -> Dict[str, torch.Tensor]:
+    """The perspective counterpart of epipolar_precision: a match i is correct when |proj(transformation['H'], keypoints0[i]) -
+    keypoints1[matches0[i]]| < threshold pixels (fp64) -> {'precision' [B] = correct / matched, 'matching_score' [B] = correct /
+    num_keypoints0, both fp32 and 0 when nothing is matched, 'num_correct' [B] int32}.  Shapes as geometry.homography."""
+    s0, s1, sm = (geometry._shape(t, n) for t, n in ((keypoints0, "keypoints0"), (keypoints1, "keypoints1"), (matches0, "matches0")))
+    if len(s0) != 3 or s0[2] != 2 or len(s1) != 3 or s1[2] != 2 or s1[0] != s0[0] or s0[0] == 0:
+        raise ValueError(f"keypoints0 / keypoints1 must be [B, M, 2] / [B, N, 2] with B > 0, got {list(s0)} / {list(s1)}")
+    B, M, N = s0[0], s0[1], s1[1]
+    if sm != (B, M):
+        raise ValueError(f"matches0 must be [B, M] = [{B}, {M}], got {list(sm)}")
+    if num_keypoints0 is not None and geometry._shape(num_keypoints0, "num_keypoints0") != (B,):
+        raise ValueError(f"num_keypoints0 must be [B] = [{B}], got {list(num_keypoints0.shape)}")
+    if not float(threshold) >= 0.0:
+        raise ValueError(f"threshold must be non-negative, got {threshold}")
+    Ht = _true_h(transformation, B)
+    k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
+    k1 = _lib.gpu_tensor(keypoints1, "keypoints1", convert=True)
+    m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
+    nk = None if num_keypoints0 is None else _lib.gpu_tensor(num_keypoints0, "num_keypoints0", torch.int32, convert=True)
+    dev = k0.device
+    prec = torch.empty(B, device=dev, dtype=torch.float32)
+    score = torch.empty(B, device=dev, dtype=torch.float32)
+    correct = torch.empty(B, device=dev, dtype=torch.int32)
+    _lib.call("og_homography_precision", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), Ht.data_ptr(),
+              float(threshold), prec.data_ptr(), score.data_ptr(), correct.data_ptr(), _lib.STREAM)
+    return {"precision": prec, "matching_score": score, "num_correct": correct}
+
+
+def homography_error(H_est, H_true, image_size) -> torch.Tensor:
+    """Mean corner error: the four corners of an image of image_size = (width, height) mapped by H_est [B, 3, 3] (float64, as
+    geometry.homography returns it; any scale) and by H_true [B, 3, 3] (float32) -> the mean distance in pixels [B] fp32, +inf for an
+    all-zero estimate (no model) or a non-finite projection."""
+    se, st = geometry._shape(H_est, "H_est"), geometry._shape(H_true, "H_true")
+    if len(se) != 3 or se[1:] != (3, 3) or st != se or se[0] == 0:
+        raise ValueError(f"H_est / H_true must both be [B, 3, 3] with B > 0, got {list(se)} / {list(st)}")
+    width, height = (int(v) for v in image_size)
+    if width <= 0 or height <= 0:
+        raise ValueError(f"image_size must be (width, height) with both positive, got {image_size}")
+    He = _lib.gpu_tensor(H_est, "H_est", torch.float64, convert=True)
+    Ht = _lib.gpu_tensor(H_true, "H_true", convert=True)
+    err = torch.empty(se[0], device=He.device, dtype=torch.float32)
+    _lib.call("og_homography_corner_error", He.device, se[0], He.data_ptr(), Ht.data_ptr(), width, height, err.data_ptr(), _lib.STREAM)
+    return err
+
+
+class HomographyAccuracy:
+    """AccuracyUsingEpipolarDist for perspective items (transformation['H']): mean precision and matching score, a match being
+    correct within `threshold` pixels of where the true homography sends its keypoint."""
+
+    def __init__(self, threshold=3.0):
+        self.threshold = threshold
+        self.reset()
+
+    def reset(self):
+        self.precision = []
+        self.matching_score = []
+
+    def update(self, matched_kpts0, matched_kpts1, transformation, num_detected_kpts):
+        """One pair: matched keypoints [K, 2] of both images, transformation with H [3, 3]."""
+        kp0, kp1, m0, nk = _pad_pair(matched_kpts0, matched_kpts1, num_detected_kpts)
+        self.update_batch(kp0, kp1, m0, {"H": _lib.gpu_tensor(transformation["H"], "transformation['H']", convert=True).unsqueeze(0)}, nk)
+
+    def update_batch(self, keypoints0, keypoints1, matches0, transformation, num_keypoints0=None):
+        """A SuperGlue.match batch, as AccuracyUsingEpipolarDist.update_batch, with transformation['H'] [B, 3, 3]."""
+        r = homography_precision(keypoints0, keypoints1, matches0, transformation, num_keypoints0, self.threshold)
+        self.precision.append(r["precision"])
+        self.matching_score.append(r["matching_score"])
+
+    def __call__(self, *args, **kwargs):
+        self.update(*args, **kwargs)
+
+    def compute(self):
+        return {
+            'Precision': torch.cat(self.precision).mean(),
+            'Matching Score': torch.cat(self.matching_score).mean(),
+        }
+
+
+class HomographyAUC:
+    """CameraPoseAUC for perspective items: a homography per pair by geometry.homography (RANSAC threshold
+    `ransac_inliers_threshold` pixels), its mean corner error against transformation['H'] over an image of image_size = (width,
+    height), AUC of that error at `auc_thresholds` (pixels).  A pair without a model counts with an infinite error."""
+
+    def __init__(self, auc_thresholds: Sequence[float], ransac_inliers_threshold: float, image_size, hypotheses: int = 2048, seed: int = 0):
+        self.auc_thresholds = auc_thresholds
+        self.ransac_inliers_threshold = ransac_inliers_threshold
+        self.image_size = image_size
+        self.hypotheses = hypotheses
+        self.seed = seed
+        self.reset()
+
+    def reset(self):
+        self.corner_errors = []
+        self._pairs = 0          # pairs seen: the pair index of the RANSAC draws
+
+    def update(self, matched_kpts0, matched_kpts1, transformation):
+        kp0, kp1, m0, _ = _pad_pair(matched_kpts0, matched_kpts1)
+        self.update_batch(kp0, kp1, m0, {"H": _lib.gpu_tensor(transformation["H"], "transformation['H']", convert=True).unsqueeze(0)})
+
+    def update_batch(self, keypoints0, keypoints1, matches0, transformation, num_keypoints0=None):
+        B = geometry._shape(keypoints0, "keypoints0")[0]
+        Ht = _true_h(transformation, B)
+        r = geometry.homography(keypoints0, keypoints1, matches0, num_keypoints0, threshold=self.ransac_inliers_threshold,
+                                hypotheses=self.hypotheses, seed=self.seed, pair_offset=self._pairs)
+        self._pairs += B
+        self.corner_errors.append(homography_error(r["H"], Ht, self.image_size))
+
+    def __call__(self, *args, **kwargs):
+        self.update(*args, **kwargs)
+
+    def compute(self):
+        return {k[:-3] + "px": v for k, v in pose_auc(torch.cat(self.corner_errors), self.auc_thresholds).items()}      # 'AUC@{t}deg'
 
 
 def pose_auc(errors: torch.Tensor, auc_thresholds: Sequence[float]) -> Dict[str, torch.Tensor]:
