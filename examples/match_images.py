@@ -4,10 +4,13 @@ The pair is related by a homography, which is degenerate for a fundamental matri
 count is shown, the accuracy of the stage is the business of tests/test_gpu_geometry.py.
 
     python examples/match_images.py [--size 480x640] [--keypoints 2048] [--match-threshold 0.2] [--features {superpoint,sift,dog_affnet_hardnet}]
-                                    [--verify {fundamental,homography}]
+                                    [--verify {fundamental,homography}] [--scoring {inliers,sigma}]
 
 --verify homography runs find_homography (cv2.findHomography(..., cv2.RANSAC, 3.0)) as the last stage instead, the model that fits
 this planar pair, and prints its inliers and the mean corner error against the homography the pair was made with.
+
+--scoring sigma scores the last stage by MAGSAC++'s sigma-consensus with weighted refits (geometry.py), which is what the reference's
+cv2.USAC_MAGSAC does; the default counts inliers.
 
 --features sift runs the reference's 128-d pipeline: the SIFT extractor (openglue_amd/sift.py) and a 128-d SuperGlue.
 --features dog_affnet_hardnet runs DoG + AffNet + OriNet + HardNet (openglue_amd/affnet_hardnet.py, seeded weights) with the affine
@@ -41,13 +44,15 @@ def main():
     ap.add_argument("--match-threshold", type=float, default=0.2)
     ap.add_argument("--features", choices=("superpoint", "sift", "dog_affnet_hardnet"), default="superpoint")
     ap.add_argument("--verify", choices=("fundamental", "homography"), default="fundamental")
+    ap.add_argument("--scoring", choices=("inliers", "sigma"), default="inliers")
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.split("x"))
     dev = torch.device("cuda:0")
     img0 = syn.make_image(H, W, seed=1)
     Hm = syn.random_homography(H, W, seed=2)
     img1 = syn.warp_image(img0, Hm)
-    verify = find_homography if a.verify == "homography" else find_fundamental
+    find = find_homography if a.verify == "homography" else find_fundamental
+    verify = (lambda k0, k1: find(k0, k1, scoring="sigma")) if a.scoring == "sigma" else find
     affine = a.features == "dog_affnet_hardnet"
     if a.features == "sift":
         sp = SIFT(max_keypoints=a.keypoints).to(dev)

@@ -625,6 +625,36 @@ int og_homography_precision(int32_t batch, int32_t m, int32_t n, const float* ke
 int og_homography_corner_error(int32_t batch, const double* H_est, const float* H_true, int32_t width, int32_t height, float* error,
                                void* stream);
 
+/* Sigma-consensus scoring (MAGSAC++, what cv2.USAC_MAGSAC scores with) for the two estimators above (csrc/sigma_consensus.hip over
+ * the kernels of geometry.hip / homography.hip).  Added to ABI v14 without a version bump: three new entries, nothing existing
+ * changes.  Constants as OpenCV's: 4 degrees of freedom, a = 1.5, k = 3.64, sigma_max = threshold / k, u_max = k^2 / 2.  With e a
+ * match's squared residual (pixels^2: Sampson for F, forward transfer for H), t = e / threshold^2 and u = t u_max,
+ *   w(t) = (G(a, u) - G(a, u_max)) / (G(a) - G(a, u_max)),   q(t) = 1 - (g(a + 1, u) + u (G(a, u) - G(a, u_max))) / g(a + 1, u_max)
+ * (G / g the upper / lower incomplete gamma function) for t <= 1, both 0 otherwise; a match with `e <= threshold^2` false (NaN and
+ * infinity included) contributes nothing, and threshold = 0 takes t = 0 for e = 0.  `threshold` is here an upper bound on the
+ * noise, not a decision boundary: below about twice the noise the weights are too tight.
+ *
+ * og_fundamental_matrix_sc / og_homography_sc: og_fundamental_matrix / og_homography with a model scored by
+ *   Q = sum over its valid matches of rint(65536 q(t)) (an integer: the winner does not depend on the order of summation); the largest
+ *   Q wins, the lowest model on ties.  The refits are the same least-squares fits over the matches with e <= threshold^2, each
+ *   match's rows weighted by w(t) under the current model; a refit is kept if it is finite and its Q is no smaller, and a round is
+ *   skipped below 8 (F) / 5 (H) such matches.  inliers, num_inliers: e <= threshold^2 under the final model, as in the plain entries;
+ *   quality [B] fp32 = Q / 65536 of the final model, the soft inlier count, 0 without a model.  Same workspace
+ *   (og_fundamental_matrix_workspace_bytes / og_homography_workspace_bytes), same draws, same refusals, and OG_E_SHAPE for m > 32768
+ *   (Q + 1 must fit 32 bits).  Four kernels, no host synchronisation, bit-identical from run to run.
+ * og_sigma_consensus_eval: t [count] fp32 -> q [count] uint32 = rint(65536 q(t)) within one unit, non-increasing in t, and w [count]
+ *   fp32 within 1.5e-6; (0, 0) for t outside [0, 1] and for NaN, (65536, 1) at t = 0.  The device function the kernels above score
+ *   with.  One kernel.  OG_E_INVALID for count <= 0 or count > 2^30. */
+int og_fundamental_matrix_sc(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                             const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
+                             int32_t refine, uint64_t seed, int64_t pair_offset, double* F, uint8_t* inliers,
+                             int32_t* num_inliers, int32_t* best_model, float* quality, void* workspace_dev, void* stream);
+int og_homography_sc(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1, const int64_t* matches0,
+                     const int32_t* num_keypoints0, float threshold, int32_t hypotheses, int32_t refine, uint64_t seed,
+                     int64_t pair_offset, double* H, uint8_t* inliers, int32_t* num_inliers, int32_t* best_model, float* quality,
+                     void* workspace_dev, void* stream);
+int og_sigma_consensus_eval(int32_t count, const float* t, uint32_t* q, float* w, void* stream);
+
 /* ABI v13 -- the SuperPoint detector / descriptor (models/features/superpoint/model.py, SuperPointNet / SuperPointNetBn), inference
  * only (eval-mode BatchNorm, folded at pack time).  descriptor_dim 256.  Image [B][H][W] fp32, H, W >= 8, B * H * W <= 2^26;
  * Hc = H / 8, Wc = W / 8 (floor, as the three 2x2 max-pools), the heatmap is [B][8 Hc][8 Wc].

@@ -185,6 +185,11 @@ SYMBOLS = {
                                 _vp, _vp, _vp, _vp, _vp, _vp]),
     "og_homography_precision": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]),
     "og_homography_corner_error": (C.c_int, [_i32, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "og_fundamental_matrix_sc": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f, _i32, _i32, C.c_uint64, _i64,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_homography_sc": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _f, _i32, _i32, C.c_uint64, _i64,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "og_sigma_consensus_eval": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
     "og_superpoint_packed_bytes": (_sz, [_i32]),
     "og_superpoint_pack": (C.c_int, [_i32, _i32, _f, _vp, _vp]),
     "og_superpoint_capacity": (C.c_int, [_i32, _i32, _i32]),

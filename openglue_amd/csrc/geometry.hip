@@ -21,6 +21,10 @@
 //                         row per lane, rank 2 through jacobi3 on F^T F, inliers recounted, kept if not fewer}, then the mask by the
 //                         same fp32 test, F back in pixels, unit norm, largest entry positive
 //    Four launches whatever the batch; no host synchronisation, no float atomics: every output is identical from run to run.
+//
+//  * og_fundamental_matrix_sc -- the same four launches with sigma-consensus scoring: the score and finish kernels are templates on
+//    the scoring mode, this unit instantiates the hard count (SC = 0), and sigma_consensus.hip includes this file with OG_SIGMA_UNIT
+//    for the SC = 1 instances and their entry.
 #include "og_common.h"
 #include "og_ransac.h"
 
@@ -280,8 +284,8 @@ __global__ void __launch_bounds__(64) fm_solve_kernel(FSolveSrc src, int count, 
 
 // Squared Sampson error in pixels^2 <= t2 on normalised coordinates q = (u0, v0, u1, v1), x_pixel = x / s + c: the numerator
 // x1^T F x0 is the same in both frames, the gradient of image 0 carries that image's scale s0 and likewise s1 (s0sq, s1sq: the squares).
-// fp32, explicit FMAs: the score and finish kernels agree bitwise.
-__device__ __forceinline__ bool sampson_inlier_px(const float (&e)[9], float4 q, float s0sq, float s1sq, float t2) {
+// fp32, explicit FMAs: the score and finish kernels agree bitwise.  sampson_px is the error, which sigma-consensus scoring weighs.
+__device__ __forceinline__ float sampson_px(const float (&e)[9], float4 q, float s0sq, float s1sq) {
     const float a0 = __fmaf_rn(e[0], q.x, __fmaf_rn(e[1], q.y, e[2]));
     const float a1 = __fmaf_rn(e[3], q.x, __fmaf_rn(e[4], q.y, e[5]));
     const float a2 = __fmaf_rn(e[6], q.x, __fmaf_rn(e[7], q.y, e[8]));
@@ -291,11 +295,22 @@ __device__ __forceinline__ bool sampson_inlier_px(const float (&e)[9], float4 q,
     const float g1 = __fmaf_rn(a0, a0, __fmul_rn(a1, a1));        // |d/dx1|^2 / s1^2
     const float g0 = __fmaf_rn(b0, b0, __fmul_rn(b1, b1));        // |d/dx0|^2 / s0^2
     const float den = __fmaf_rn(s1sq, g1, __fmul_rn(s0sq, g0));
-    return __fdiv_rn(__fmul_rn(num, num), den) <= t2;
+    return __fdiv_rn(__fmul_rn(num, num), den);
+}
+__device__ __forceinline__ bool sampson_inlier_px(const float (&e)[9], float4 q, float s0sq, float s1sq, float t2) {
+    return sampson_px(e, q, s0sq, s1sq) <= t2;
 }
 
+// SC = 0: a model's score is its number of inliers.  SC = 1: sigma-consensus, the score is Q = sum of q in units of 2^-16 (og_ransac.h).
+template <int SC>
 __global__ void __launch_bounds__(256) fm_score_kernel(FundWs w, int m, int H, int groups, float t2) {
     __shared__ float4 pts[kFChunk];
+    const float* sig = nullptr;
+    if constexpr (SC) {
+        __shared__ float tab[kSigmaCells + 1];
+        sigma_table_fill(tab);                               // the barriers of the first chunk come before its first use
+        sig = tab;
+    }
     const int b = blockIdx.x / groups;                       // `groups` workgroups per pair, pair-major along x
     const int model = (blockIdx.x - b * groups) * 256 + threadIdx.x;        // h * 3 + s
     const int h = model / kFSol, s = model - h * kFSol;
@@ -306,16 +321,30 @@ __global__ void __launch_bounds__(256) fm_score_kernel(FundWs w, int m, int H, i
     for (int c = 0; c < 9; ++c) e[c] = live ? (float)w.F[prob * kFSlots + s * 9 + c] : 0.0f;
     const int n = w.count[b];
     const float s0sq = (float)(w.norm[(int64_t)b * 6 + 2] * w.norm[(int64_t)b * 6 + 2]), s1sq = (float)(w.norm[(int64_t)b * 6 + 5] * w.norm[(int64_t)b * 6 + 5]);
+    const float inv_t2 = sigma_inv_bound(t2);                // SC = 1 only
     int inl = 0;
+    uint32_t Q = 0u;
     for (int k0 = 0; k0 < n; k0 += kFChunk) {
         const int len = min(kFChunk, n - k0);
         __syncthreads();
         for (int k = threadIdx.x; k < len; k += 256) pts[k] = to_f4(w.pts[(int64_t)b * m + k0 + k]);
         __syncthreads();
-        if (live)
-            for (int k = 0; k < len; ++k) inl += sampson_inlier_px(e, pts[k], s0sq, s1sq, t2);
+        if constexpr (SC) {
+            if (live)
+#pragma unroll 4
+                for (int k = 0; k < len; ++k) {
+                    uint32_t q;
+                    float wt;
+                    sigma_match(sig, sampson_px(e, pts[k], s0sq, s1sq), t2, inv_t2, q, wt);
+                    Q += q;
+                }
+        } else {
+            if (live)
+                for (int k = 0; k < len; ++k) inl += sampson_inlier_px(e, pts[k], s0sq, s1sq, t2);
+        }
     }
-    const unsigned long long key = live ? ((unsigned long long)(inl + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)model) : 0ull;
+    const unsigned long long score = SC ? (unsigned long long)Q : (unsigned long long)inl;
+    const unsigned long long key = live ? ((score + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)model) : 0ull;
     publish_best(key, &w.best[b]);
 }
 
@@ -345,8 +374,18 @@ __device__ inline bool rank2_unit(double (&F)[9]) {
     return finite(inv);
 }
 
+// SC as in fm_score_kernel.  SC = 1: the refit's rows are weighted by w, a refit is kept if its Q is no smaller, and the last argument
+// is `float* quality`, Q / 65536 of the final model.
+template <int SC, class... Quality>
 __global__ void __launch_bounds__(256) fm_finish_kernel(FGeo g, FundWs w, int H, int refine, float t2, double* F_out, uint8_t* inliers,
-                                                        int* num_inliers, int* best_model) {
+                                                        int* num_inliers, int* best_model, Quality... quality) {
+    const float* sig = nullptr;
+    if constexpr (SC) {
+        __shared__ float tab[kSigmaCells + 1];
+        sigma_table_fill(tab);
+        __syncthreads();
+        sig = tab;
+    }
     __shared__ double racc[4][45];
     __shared__ double fnew[10];          // the refit and 1.0 if it is sound
     __shared__ int red[4];
@@ -364,6 +403,7 @@ __global__ void __launch_bounds__(256) fm_finish_kernel(FGeo g, FundWs w, int H,
             for (int c = 0; c < 9; ++c) F_out[(int64_t)b * 9 + c] = 0.0;
             num_inliers[b] = 0;
             best_model[b] = -1;
+            store_quality(b, 0.0f, quality...);
         }
         return;
     }
@@ -373,12 +413,28 @@ __global__ void __launch_bounds__(256) fm_finish_kernel(FGeo g, FundWs w, int H,
     float e[9];
 #pragma unroll
     for (int c = 0; c < 9; ++c) { Fc[c] = w.F[((int64_t)b * H + h) * kFSlots + s * 9 + c]; e[c] = (float)Fc[c]; }
+    const float inv_t2 = sigma_inv_bound(t2);                // SC = 1 only
     auto count_inliers = [&](const float (&f)[9]) {
         int c = 0;
         for (int k = threadIdx.x; k < n; k += 256) c += sampson_inlier_px(f, to_f4(P[k]), s0sq, s1sq, t2);
         return block_sum(c, red);
     };
-    int cur = count_inliers(e);
+    // sigma-consensus: the inliers of a model to cnt and its Q returned, one pass
+    auto measure = [&](const float (&f)[9], int& cnt) {
+        int c = 0;
+        uint32_t Q = 0u;
+        for (int k = threadIdx.x; k < n; k += 256) {
+            uint32_t q;
+            float wt;
+            c += sigma_match(sig, sampson_px(f, to_f4(P[k]), s0sq, s1sq), t2, inv_t2, q, wt);
+            Q += q;
+        }
+        cnt = block_sum(c, red);
+        return block_sum(Q, (uint32_t*)red);
+    };
+    int cur;
+    uint32_t curq = 0u;
+    if constexpr (SC) curq = measure(e, cur); else cur = count_inliers(e);
     for (int round = 0; round < refine; ++round) {
         if (cur < 8) break;
         double acc[45];
@@ -386,12 +442,20 @@ __global__ void __launch_bounds__(256) fm_finish_kernel(FGeo g, FundWs w, int H,
         for (int c = 0; c < 45; ++c) acc[c] = 0.0;
         for (int k = threadIdx.x; k < n; k += 256) {
             const double4 q = P[k];
-            if (!sampson_inlier_px(e, to_f4(q), s0sq, s1sq, t2)) continue;
+            uint32_t qk;
+            float wt;
+            if constexpr (SC) {
+                if (!sigma_match(sig, sampson_px(e, to_f4(q), s0sq, s1sq), t2, inv_t2, qk, wt)) continue;
+            } else {
+                if (!sampson_inlier_px(e, to_f4(q), s0sq, s1sq, t2)) continue;
+            }
             const double r[9] = {q.z * q.x, q.z * q.y, q.z, q.w * q.x, q.w * q.y, q.w, q.x, q.y, 1.0};
 #pragma unroll
-            for (int i = 0; i < 9; ++i)
+            for (int i = 0; i < 9; ++i) {
+                const double ri = SC ? (double)wt * r[i] : r[i];      // the weighted row: one multiply per entry
 #pragma unroll
-                for (int j = i; j < 9; ++j) acc[tri(i, j)] += r[i] * r[j];
+                for (int j = i; j < 9; ++j) acc[tri(i, j)] += ri * r[j];
+            }
         }
 #pragma unroll
         for (int c = 0; c < 45; ++c) {
@@ -442,9 +506,12 @@ __global__ void __launch_bounds__(256) fm_finish_kernel(FGeo g, FundWs w, int H,
 #pragma unroll
         for (int c = 0; c < 9; ++c) { Fn[c] = fnew[c]; en[c] = (float)Fn[c]; }
         const bool sound = fnew[9] == 1.0;
-        const int cnt = count_inliers(en);              // its barriers also keep fnew until every lane has read it
-        if (sound && cnt >= cur) {
+        int cnt;                                        // the count's barriers also keep fnew until every lane has read it
+        uint32_t qn = 0u;
+        if constexpr (SC) qn = measure(en, cnt); else cnt = count_inliers(en);
+        if (sound && (SC ? qn >= curq : cnt >= cur)) {
             cur = cnt;
+            curq = qn;
 #pragma unroll
             for (int c = 0; c < 9; ++c) { Fc[c] = Fn[c]; e[c] = en[c]; }
         }
@@ -477,34 +544,22 @@ __global__ void __launch_bounds__(256) fm_finish_kernel(FGeo g, FundWs w, int H,
     for (int c = 0; c < 9; ++c) F_out[(int64_t)b * 9 + c] = Fp[c] * inv;
     num_inliers[b] = cur;
     best_model[b] = model;
+    store_quality(b, (float)((double)curq / 65536.0), quality...);
 }
 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C ABI
-extern "C" int og_fundamental_7pt(int32_t count, const double* x0, const double* x1, double* F, int32_t* num_solutions, void* stream) {
-    og_clear_status();
-    if (count <= 0 || count > (1 << 30) || !x0 || !x1 || !F || !num_solutions) return OG_E_INVALID;
-    FSolveSrc src{};
-    src.x0 = x0; src.x1 = x1;
-    hipLaunchKernelGGL(fm_solve_kernel, dim3((count + 63) / 64), dim3(64), 0, (hipStream_t)stream, src, count, F, num_solutions);
-    return og_launch_status();
-}
-
 static bool fund_sizes_ok(int32_t batch, int32_t m, int32_t hypotheses) {
     return batch > 0 && m >= 0 && hypotheses > 0 && (int64_t)kFSol * batch * hypotheses <= (1 << 30);
 }
 
-extern "C" size_t og_fundamental_matrix_workspace_bytes(int32_t batch, int32_t m, int32_t hypotheses) {
-    if (!fund_sizes_ok(batch, m, hypotheses)) return 0;
-    return fund_bytes(batch, m, hypotheses);
-}
-
-extern "C" int og_fundamental_matrix(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
-                                     const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
-                                     int32_t refine, uint64_t seed, int64_t pair_offset, double* F, uint8_t* inliers,
-                                     int32_t* num_inliers, int32_t* best_model, void* workspace_dev, void* stream) {
-    og_clear_status();
+// The four launches of og_fundamental_matrix (SC = 0) and og_fundamental_matrix_sc (SC = 1, quality = one float*).
+template <int SC, class... Quality>
+static int fund_run(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1, const int64_t* matches0,
+                    const int32_t* num_keypoints0, float threshold, int32_t hypotheses, int32_t refine, uint64_t seed, int64_t pair_offset,
+                    double* F, uint8_t* inliers, int32_t* num_inliers, int32_t* best_model, void* workspace_dev, void* stream,
+                    Quality... quality) {
     if (!fund_sizes_ok(batch, m, hypotheses) || n < 0 || refine < 0 || !(threshold >= 0.0f) || !F || !num_inliers || !best_model ||
         !workspace_dev)
         return OG_E_INVALID;
@@ -520,7 +575,44 @@ extern "C" int og_fundamental_matrix(int32_t batch, int32_t m, int32_t n, const 
     hipLaunchKernelGGL(fm_prep_kernel, dim3(batch), dim3(256), 0, st, g, w);
     hipLaunchKernelGGL(fm_solve_kernel, dim3((count + 63) / 64), dim3(64), 0, st, src, count, w.F, w.nsol);
     const int groups = (hypotheses * kFSol + 255) / 256;      // batch * groups <= 2^22 + batch by the size rule: one grid dimension
-    hipLaunchKernelGGL(fm_score_kernel, dim3(batch * groups), dim3(256), 0, st, w, m, hypotheses, groups, t2);
-    hipLaunchKernelGGL(fm_finish_kernel, dim3(batch), dim3(256), 0, st, g, w, hypotheses, refine, t2, F, inliers, num_inliers, best_model);
+    hipLaunchKernelGGL(fm_score_kernel<SC>, dim3(batch * groups), dim3(256), 0, st, w, m, hypotheses, groups, t2);
+    hipLaunchKernelGGL((fm_finish_kernel<SC, Quality...>), dim3(batch), dim3(256), 0, st, g, w, hypotheses, refine, t2, F, inliers,
+                       num_inliers, best_model, quality...);
     return og_launch_status();
 }
+
+#ifdef OG_SIGMA_UNIT      // sigma_consensus.hip includes this file for the SC = 1 instances, so that this unit holds the four kernels it held
+extern "C" int og_fundamental_matrix_sc(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                                        const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
+                                        int32_t refine, uint64_t seed, int64_t pair_offset, double* F, uint8_t* inliers,
+                                        int32_t* num_inliers, int32_t* best_model, float* quality, void* workspace_dev, void* stream) {
+    og_clear_status();
+    if (!quality) return OG_E_INVALID;
+    if (m > kSigmaMaxMatches) return OG_E_SHAPE;
+    return fund_run<1>(batch, m, n, keypoints0, keypoints1, matches0, num_keypoints0, threshold, hypotheses, refine, seed, pair_offset, F,
+                       inliers, num_inliers, best_model, workspace_dev, stream, quality);
+}
+#else
+extern "C" int og_fundamental_7pt(int32_t count, const double* x0, const double* x1, double* F, int32_t* num_solutions, void* stream) {
+    og_clear_status();
+    if (count <= 0 || count > (1 << 30) || !x0 || !x1 || !F || !num_solutions) return OG_E_INVALID;
+    FSolveSrc src{};
+    src.x0 = x0; src.x1 = x1;
+    hipLaunchKernelGGL(fm_solve_kernel, dim3((count + 63) / 64), dim3(64), 0, (hipStream_t)stream, src, count, F, num_solutions);
+    return og_launch_status();
+}
+
+extern "C" size_t og_fundamental_matrix_workspace_bytes(int32_t batch, int32_t m, int32_t hypotheses) {
+    if (!fund_sizes_ok(batch, m, hypotheses)) return 0;
+    return fund_bytes(batch, m, hypotheses);
+}
+
+extern "C" int og_fundamental_matrix(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                                     const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
+                                     int32_t refine, uint64_t seed, int64_t pair_offset, double* F, uint8_t* inliers,
+                                     int32_t* num_inliers, int32_t* best_model, void* workspace_dev, void* stream) {
+    og_clear_status();
+    return fund_run<0>(batch, m, n, keypoints0, keypoints1, matches0, num_keypoints0, threshold, hypotheses, refine, seed, pair_offset, F,
+                       inliers, num_inliers, best_model, workspace_dev, stream);
+}
+#endif

@@ -21,6 +21,10 @@
 //                         H back in pixels, unit norm, largest entry positive
 //    Four launches whatever the batch; no host synchronisation, no float atomics: every output is identical from run to run.
 //
+//  * og_homography_sc -- the same four launches with sigma-consensus scoring: the score and finish kernels are templates on the
+//    scoring mode, this unit instantiates the hard count (SC = 0), and sigma_consensus.hip includes this file with OG_SIGMA_UNIT for
+//    the SC = 1 instances and their entry.
+//
 //  * og_homography_precision -- hm_precision_kernel: per pair, |proj(H_true, k0[i]) - k1[matches0[i]]| in fp64 for every valid match
 //  * og_homography_corner_error -- hm_corner_error_kernel: mean distance of the four image corners under the estimate and the truth
 #include "og_common.h"
@@ -188,21 +192,31 @@ __global__ void __launch_bounds__(64) hm_solve_kernel(HSolveSrc src, int count, 
 
 // Squared forward transfer error |proj(H, x0) - x1|^2 <= t2s on normalised coordinates q = (u0, v0, u1, v1), x_pixel = x / s + c: a
 // distance in image 1 in pixels is the normalised one over s1, so t2s = threshold^2 s1^2.  A non-finite error (a point on the
-// line H sends to infinity) compares false.  fp32, explicit FMAs: the score and finish kernels agree bitwise.
-__device__ __forceinline__ bool transfer_inlier_px(const float (&e)[9], float4 q, float t2s) {
+// line H sends to infinity) compares false.  fp32, explicit FMAs: the score and finish kernels agree bitwise.  transfer_px is the
+// error, which sigma-consensus scoring weighs.
+__device__ __forceinline__ float transfer_px(const float (&e)[9], float4 q) {
     const float px = __fmaf_rn(e[0], q.x, __fmaf_rn(e[1], q.y, e[2]));
     const float py = __fmaf_rn(e[3], q.x, __fmaf_rn(e[4], q.y, e[5]));
     const float pw = __fmaf_rn(e[6], q.x, __fmaf_rn(e[7], q.y, e[8]));
     const float iw = __fdiv_rn(1.0f, pw);
     const float dx = __fmaf_rn(px, iw, -q.z), dy = __fmaf_rn(py, iw, -q.w);
-    return __fmaf_rn(dx, dx, __fmul_rn(dy, dy)) <= t2s;
+    return __fmaf_rn(dx, dx, __fmul_rn(dy, dy));
 }
+__device__ __forceinline__ bool transfer_inlier_px(const float (&e)[9], float4 q, float t2s) { return transfer_px(e, q) <= t2s; }
 
 // threshold^2 s1^2 in fp32, the one rounding both kernels use
 __device__ __forceinline__ float transfer_bound(float t2, double s1) { return __fmul_rn(t2, (float)(s1 * s1)); }
 
+// SC = 0: a model's score is its number of inliers.  SC = 1: sigma-consensus, the score is Q = sum of q in units of 2^-16 (og_ransac.h).
+template <int SC>
 __global__ void __launch_bounds__(256) hm_score_kernel(HomWs w, int m, int H, int groups, float t2) {
     __shared__ float4 pts[kHChunk];
+    const float* sig = nullptr;
+    if constexpr (SC) {
+        __shared__ float tab[kSigmaCells + 1];
+        sigma_table_fill(tab);                               // the barriers of the first chunk come before its first use
+        sig = tab;
+    }
     const int b = blockIdx.x / groups;                       // `groups` workgroups per pair, pair-major along x
     const int h = (blockIdx.x - b * groups) * 256 + threadIdx.x;
     const int64_t prob = (int64_t)b * H + h;
@@ -212,21 +226,45 @@ __global__ void __launch_bounds__(256) hm_score_kernel(HomWs w, int m, int H, in
     for (int c = 0; c < 9; ++c) e[c] = live ? (float)w.H[prob * kHSlots + c] : 0.0f;
     const int n = w.count[b];
     const float t2s = transfer_bound(t2, w.norm[(int64_t)b * 6 + 5]);
+    const float inv_t2 = sigma_inv_bound(t2s);               // SC = 1 only
     int inl = 0;
+    uint32_t Q = 0u;
     for (int k0 = 0; k0 < n; k0 += kHChunk) {
         const int len = min(kHChunk, n - k0);
         __syncthreads();
         for (int k = threadIdx.x; k < len; k += 256) pts[k] = to_f4(w.pts[(int64_t)b * m + k0 + k]);
         __syncthreads();
-        if (live)
-            for (int k = 0; k < len; ++k) inl += transfer_inlier_px(e, pts[k], t2s);      // every lane reads pts[k]: a broadcast
+        if constexpr (SC) {
+            if (live)
+#pragma unroll 4
+                for (int k = 0; k < len; ++k) {
+                    uint32_t q;
+                    float wt;
+                    sigma_match(sig, transfer_px(e, pts[k]), t2s, inv_t2, q, wt);
+                    Q += q;
+                }
+        } else {
+            if (live)
+                for (int k = 0; k < len; ++k) inl += transfer_inlier_px(e, pts[k], t2s);      // every lane reads pts[k]: a broadcast
+        }
     }
-    const unsigned long long key = live ? ((unsigned long long)(inl + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)h) : 0ull;
+    const unsigned long long score = SC ? (unsigned long long)Q : (unsigned long long)inl;
+    const unsigned long long key = live ? ((score + 1) << 32) | (unsigned)(0xFFFFFFFFu - (unsigned)h) : 0ull;
     publish_best(key, &w.best[b]);
 }
 
+// SC as in hm_score_kernel.  SC = 1: the refit's rows are weighted by w, a refit is kept if its Q is no smaller, and the last argument
+// is `float* quality`, Q / 65536 of the final model.
+template <int SC, class... Quality>
 __global__ void __launch_bounds__(256) hm_finish_kernel(HGeo g, HomWs w, int H, int refine, float t2, double* H_out, uint8_t* inliers,
-                                                        int* num_inliers, int* best_model) {
+                                                        int* num_inliers, int* best_model, Quality... quality) {
+    const float* sig = nullptr;
+    if constexpr (SC) {
+        __shared__ float tab[kSigmaCells + 1];
+        sigma_table_fill(tab);
+        __syncthreads();
+        sig = tab;
+    }
     __shared__ double racc[4][45];
     __shared__ double hnew[10];          // the refit and 1.0 if it is sound
     __shared__ int red[4];
@@ -243,6 +281,7 @@ __global__ void __launch_bounds__(256) hm_finish_kernel(HGeo g, HomWs w, int H, 
             for (int c = 0; c < 9; ++c) H_out[(int64_t)b * 9 + c] = 0.0;
             num_inliers[b] = 0;
             best_model[b] = -1;
+            store_quality(b, 0.0f, quality...);
         }
         return;
     }
@@ -252,12 +291,28 @@ __global__ void __launch_bounds__(256) hm_finish_kernel(HGeo g, HomWs w, int H, 
     float e[9];
 #pragma unroll
     for (int c = 0; c < 9; ++c) { Hc[c] = w.H[((int64_t)b * H + h) * kHSlots + c]; e[c] = (float)Hc[c]; }
+    const float inv_t2 = sigma_inv_bound(t2s);               // SC = 1 only
     auto count_inliers = [&](const float (&f)[9]) {
         int c = 0;
         for (int k = threadIdx.x; k < n; k += 256) c += transfer_inlier_px(f, to_f4(P[k]), t2s);
         return block_sum(c, red);
     };
-    int cur = count_inliers(e);
+    // sigma-consensus: the inliers of a model to cnt and its Q returned, one pass
+    auto measure = [&](const float (&f)[9], int& cnt) {
+        int c = 0;
+        uint32_t Q = 0u;
+        for (int k = threadIdx.x; k < n; k += 256) {
+            uint32_t q;
+            float wt;
+            c += sigma_match(sig, transfer_px(f, to_f4(P[k])), t2s, inv_t2, q, wt);
+            Q += q;
+        }
+        cnt = block_sum(c, red);
+        return block_sum(Q, (uint32_t*)red);
+    };
+    int cur;
+    uint32_t curq = 0u;
+    if constexpr (SC) curq = measure(e, cur); else cur = count_inliers(e);
     for (int round = 0; round < refine; ++round) {
         if (cur < 5) break;
         double acc[45];
@@ -265,14 +320,22 @@ __global__ void __launch_bounds__(256) hm_finish_kernel(HGeo g, HomWs w, int H, 
         for (int c = 0; c < 45; ++c) acc[c] = 0.0;
         for (int k = threadIdx.x; k < n; k += 256) {
             const double4 q = P[k];
-            if (!transfer_inlier_px(e, to_f4(q), t2s)) continue;
+            uint32_t qk;
+            float wt;
+            if constexpr (SC) {
+                if (!sigma_match(sig, transfer_px(e, to_f4(q)), t2s, inv_t2, qk, wt)) continue;
+            } else {
+                if (!transfer_inlier_px(e, to_f4(q), t2s)) continue;
+            }
             // the two DLT rows of the match: (x0^T, 0, -u1 x0^T) and (0, x0^T, -v1 x0^T)
             const double ra[9] = {q.x, q.y, 1.0, 0.0, 0.0, 0.0, -q.z * q.x, -q.z * q.y, -q.z};
             const double rb[9] = {0.0, 0.0, 0.0, q.x, q.y, 1.0, -q.w * q.x, -q.w * q.y, -q.w};
 #pragma unroll
-            for (int i = 0; i < 9; ++i)
+            for (int i = 0; i < 9; ++i) {
+                const double ai = SC ? (double)wt * ra[i] : ra[i], bi = SC ? (double)wt * rb[i] : rb[i];      // the weighted rows
 #pragma unroll
-                for (int j = i; j < 9; ++j) acc[tri(i, j)] += ra[i] * ra[j] + rb[i] * rb[j];
+                for (int j = i; j < 9; ++j) acc[tri(i, j)] += ai * ra[j] + bi * rb[j];
+            }
         }
 #pragma unroll
         for (int c = 0; c < 45; ++c) {
@@ -323,9 +386,12 @@ __global__ void __launch_bounds__(256) hm_finish_kernel(HGeo g, HomWs w, int H, 
 #pragma unroll
         for (int c = 0; c < 9; ++c) { Hn[c] = hnew[c]; en[c] = (float)Hn[c]; }
         const bool sound = hnew[9] == 1.0;
-        const int cnt = count_inliers(en);              // its barriers also keep hnew until every lane has read it
-        if (sound && cnt >= cur) {
+        int cnt;                                        // the count's barriers also keep hnew until every lane has read it
+        uint32_t qn = 0u;
+        if constexpr (SC) qn = measure(en, cnt); else cnt = count_inliers(en);
+        if (sound && (SC ? qn >= curq : cnt >= cur)) {
             cur = cnt;
+            curq = qn;
 #pragma unroll
             for (int c = 0; c < 9; ++c) { Hc[c] = Hn[c]; e[c] = en[c]; }
         }
@@ -359,8 +425,10 @@ __global__ void __launch_bounds__(256) hm_finish_kernel(HGeo g, HomWs w, int H, 
     for (int c = 0; c < 9; ++c) H_out[(int64_t)b * 9 + c] = Hp[c] * inv;
     num_inliers[b] = cur;
     best_model[b] = h;
+    store_quality(b, (float)((double)curq / 65536.0), quality...);
 }
 
+#ifndef OG_SIGMA_UNIT
 // ------------------------------------------------------------------------------------------------ metrics
 // (x, y) under the row-major 3 x 3 Hm, fp64; a point at infinity gives inf or NaN
 __device__ inline void project(const double (&Hm)[9], double x, double y, double& u, double& v) {
@@ -424,33 +492,21 @@ __global__ void __launch_bounds__(64) hm_corner_error_kernel(int B, const double
     const double mean = 0.25 * sum;
     error[b] = (any && finite(mean)) ? (float)mean : __builtin_huge_valf();
 }
+#endif
 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C ABI
-extern "C" int og_homography_4pt(int32_t count, const double* x0, const double* x1, double* H, int32_t* num_solutions, void* stream) {
-    og_clear_status();
-    if (count <= 0 || count > (1 << 30) || !x0 || !x1 || !H || !num_solutions) return OG_E_INVALID;
-    HSolveSrc src{};
-    src.x0 = x0; src.x1 = x1;
-    hipLaunchKernelGGL(hm_solve_kernel, dim3((count + 63) / 64), dim3(64), 0, (hipStream_t)stream, src, count, H, num_solutions);
-    return og_launch_status();
-}
-
 static bool hom_sizes_ok(int32_t batch, int32_t m, int32_t hypotheses) {
     return batch > 0 && m >= 0 && hypotheses > 0 && (int64_t)batch * hypotheses <= (1 << 30);
 }
 
-extern "C" size_t og_homography_workspace_bytes(int32_t batch, int32_t m, int32_t hypotheses) {
-    if (!hom_sizes_ok(batch, m, hypotheses)) return 0;
-    return hom_bytes(batch, m, hypotheses);
-}
-
-extern "C" int og_homography(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
-                             const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
-                             int32_t refine, uint64_t seed, int64_t pair_offset, double* H, uint8_t* inliers, int32_t* num_inliers,
-                             int32_t* best_model, void* workspace_dev, void* stream) {
-    og_clear_status();
+// The four launches of og_homography (SC = 0) and og_homography_sc (SC = 1, quality = one float*).
+template <int SC, class... Quality>
+static int hom_run(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1, const int64_t* matches0,
+                   const int32_t* num_keypoints0, float threshold, int32_t hypotheses, int32_t refine, uint64_t seed, int64_t pair_offset,
+                   double* H, uint8_t* inliers, int32_t* num_inliers, int32_t* best_model, void* workspace_dev, void* stream,
+                   Quality... quality) {
     if (!hom_sizes_ok(batch, m, hypotheses) || n < 0 || refine < 0 || !(threshold >= 0.0f) || !H || !num_inliers || !best_model ||
         !workspace_dev)
         return OG_E_INVALID;
@@ -466,9 +522,45 @@ extern "C" int og_homography(int32_t batch, int32_t m, int32_t n, const float* k
     hipLaunchKernelGGL(hm_prep_kernel, dim3(batch), dim3(256), 0, st, g, w);
     hipLaunchKernelGGL(hm_solve_kernel, dim3((count + 63) / 64), dim3(64), 0, st, src, count, w.H, w.nsol);
     const int groups = (hypotheses + 255) / 256;              // batch * groups <= 2^22 + batch by the size rule: one grid dimension
-    hipLaunchKernelGGL(hm_score_kernel, dim3(batch * groups), dim3(256), 0, st, w, m, hypotheses, groups, t2);
-    hipLaunchKernelGGL(hm_finish_kernel, dim3(batch), dim3(256), 0, st, g, w, hypotheses, refine, t2, H, inliers, num_inliers, best_model);
+    hipLaunchKernelGGL(hm_score_kernel<SC>, dim3(batch * groups), dim3(256), 0, st, w, m, hypotheses, groups, t2);
+    hipLaunchKernelGGL((hm_finish_kernel<SC, Quality...>), dim3(batch), dim3(256), 0, st, g, w, hypotheses, refine, t2, H, inliers,
+                       num_inliers, best_model, quality...);
     return og_launch_status();
+}
+
+#ifdef OG_SIGMA_UNIT      // sigma_consensus.hip includes this file for the SC = 1 instances, so that this unit holds the six kernels it held
+extern "C" int og_homography_sc(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                                const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
+                                int32_t refine, uint64_t seed, int64_t pair_offset, double* H, uint8_t* inliers, int32_t* num_inliers,
+                                int32_t* best_model, float* quality, void* workspace_dev, void* stream) {
+    og_clear_status();
+    if (!quality) return OG_E_INVALID;
+    if (m > kSigmaMaxMatches) return OG_E_SHAPE;
+    return hom_run<1>(batch, m, n, keypoints0, keypoints1, matches0, num_keypoints0, threshold, hypotheses, refine, seed, pair_offset, H,
+                      inliers, num_inliers, best_model, workspace_dev, stream, quality);
+}
+#else
+extern "C" int og_homography_4pt(int32_t count, const double* x0, const double* x1, double* H, int32_t* num_solutions, void* stream) {
+    og_clear_status();
+    if (count <= 0 || count > (1 << 30) || !x0 || !x1 || !H || !num_solutions) return OG_E_INVALID;
+    HSolveSrc src{};
+    src.x0 = x0; src.x1 = x1;
+    hipLaunchKernelGGL(hm_solve_kernel, dim3((count + 63) / 64), dim3(64), 0, (hipStream_t)stream, src, count, H, num_solutions);
+    return og_launch_status();
+}
+
+extern "C" size_t og_homography_workspace_bytes(int32_t batch, int32_t m, int32_t hypotheses) {
+    if (!hom_sizes_ok(batch, m, hypotheses)) return 0;
+    return hom_bytes(batch, m, hypotheses);
+}
+
+extern "C" int og_homography(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
+                             const int64_t* matches0, const int32_t* num_keypoints0, float threshold, int32_t hypotheses,
+                             int32_t refine, uint64_t seed, int64_t pair_offset, double* H, uint8_t* inliers, int32_t* num_inliers,
+                             int32_t* best_model, void* workspace_dev, void* stream) {
+    og_clear_status();
+    return hom_run<0>(batch, m, n, keypoints0, keypoints1, matches0, num_keypoints0, threshold, hypotheses, refine, seed, pair_offset, H,
+                      inliers, num_inliers, best_model, workspace_dev, stream);
 }
 
 extern "C" int og_homography_precision(int32_t batch, int32_t m, int32_t n, const float* keypoints0, const float* keypoints1,
@@ -491,3 +583,4 @@ extern "C" int og_homography_corner_error(int32_t batch, const double* H_est, co
                        height, error);
     return og_launch_status();
 }
+#endif

@@ -4,6 +4,7 @@
 // The workgroup sum and the compaction rank come from og_block.h.
 #pragma once
 #include "og_block.h"
+#include "og_sigma_table.h"
 
 namespace {
 
@@ -95,6 +96,65 @@ __device__ __forceinline__ void publish_best(unsigned long long key, unsigned lo
     }
     if ((threadIdx.x & 63) == 0 && key) atomicMax(best, key);
 }
+
+// ------------------------------------------------------------------------------------------------ sigma-consensus (MAGSAC++)
+// n = 4 degrees of freedom, a = 1.5, k = 3.64, sigma_max = threshold / k.  With t = e / threshold^2 and u = t u_max, u_max = k^2 / 2:
+//   w(t) = (G(1.5, u) - G(1.5, u_max)) / (G(1.5) - G(1.5, u_max)),                  G the upper incomplete gamma function,
+//   q(t) = 1 - (g(2.5, u) + u (G(1.5, u) - G(1.5, u_max))) / g(2.5, u_max),          g the lower one,
+// both 1 at t = 0, 0 at t = 1 and decreasing.  G(1.5, u) = sqrt(u) exp(-u) + (sqrt(pi) / 2) erfc(sqrt u), and with
+// g(2.5, u) = 1.5 g(1.5, u) - u^1.5 exp(-u) the numerator of q is 1.5 g(1.5, u) + u ((sqrt(pi) / 2) erfc(sqrt u) - G(1.5, u_max)).
+constexpr int kSigmaCells = 1024;                         // the q table: kSigmaCells + 1 floats of LDS
+constexpr int kSigmaMaxMatches = 32768;                   // Q + 1 <= 2^31 + 1 fits the upper half of the packed key
+constexpr double kSigmaUmax = 6.6248;                     // 3.64^2 / 2
+constexpr double kSigmaHalfSqrtPi = 0.88622692545275801;  // G(1.5)
+constexpr double kSigmaG1 = 0.0036572608340910764;        // G(1.5, u_max)
+
+// The table (og_sigma_table.h: 65536 q at t = i / kSigmaCells, i = 0 .. kSigmaCells, rounded to fp32 from 40 digits, decreasing from
+// 65536 to 0) into LDS by the whole workgroup (256 threads).  The caller puts a barrier before the first sigma_consensus.
+__device__ inline void sigma_table_fill(float* tab) {
+    for (int i = threadIdx.x; i <= kSigmaCells; i += 256) tab[i] = kSigmaQTable[i];
+}
+
+// fp32 t -> (q in units of 2^-16, w); (0, 0) outside [0, 1] and for NaN.  The one function of the score kernels, the finish kernels
+// and og_sigma_consensus_eval, so that they agree bitwise.
+//  q: the table, linear inside a cell.  t * kSigmaCells, the cell and the fraction are exact in fp32, the FMA is monotone in the
+//     fraction and the result never passes the cell's far end, so q does not increase with t: a closed form in fp32 cannot promise
+//     that where q is flat (its terms of order 1 cancel to q, leaving 1e-7 of noise on steps smaller than that).  The chord's error is
+//     at most q'' h^2 / 8 = 14.5 / 1024^2 / 8 = 1.7e-6, 0.11 units.
+//  w: the closed form in fp32 with explicit roundings; at t = 0 numerator and denominator are the same float, so w = 1.
+__device__ __forceinline__ void sigma_consensus(const float* tab, float t, uint32_t& q, float& w) {
+    const bool in = t >= 0.0f && t <= 1.0f;
+    const float tc = in ? t : 1.0f;                         // no branch: outside, the far end is evaluated, where q is 0 by itself
+    const float x = __fmul_rn(tc, (float)kSigmaCells);
+    const int i = min((int)x, kSigmaCells - 1);
+    const float f = x - (float)i;
+    const float q0 = tab[i], q1 = tab[i + 1];
+    q = (uint32_t)__float2int_rn(fmaxf(__fmaf_rn(f, q1 - q0, q0), q1));      // at tc = 1: fma(1, 0 - q0, q0) = 0
+    constexpr float hp = (float)kSigmaHalfSqrtPi, g1 = (float)kSigmaG1;
+    const float u = __fmul_rn(tc, (float)kSigmaUmax), s = sqrtf(u);
+    const float gu = __fmaf_rn(s, expf(-u), __fmul_rn(hp, erfcf(s)));
+    w = in ? fminf(fmaxf(__fdiv_rn(gu - g1, hp - g1), 0.0f), 1.0f) : 0.0f;
+}
+
+// 1 / t2 for sigma_match, taken once per kernel; 0 when the bound is 0 (or so small that its reciprocal overflows).
+__device__ __forceinline__ float sigma_inv_bound(float t2) {
+    const float r = __fdiv_rn(1.0f, t2);
+    return r < __builtin_huge_valf() ? r : 0.0f;
+}
+
+// A match of squared residual e under the bound t2 (both in the same units; inv_t2 = sigma_inv_bound(t2)): false, q = 0, w = 0 unless
+// e <= t2, which covers a NaN or infinite e; otherwise t = min(e * inv_t2, 1), e / t2 to 1.5 ulp without a division per match, and
+// t = 0 when the bound is 0.  No branch either: the score loop runs one model per lane, and a branch around the lookup would leave
+// each iteration waiting for its own LDS gather.
+__device__ __forceinline__ bool sigma_match(const float* tab, float e, float t2, float inv_t2, uint32_t& q, float& w) {
+    const bool inl = e <= t2;
+    sigma_consensus(tab, inl ? fminf(__fmul_rn(e, inv_t2), 1.0f) : 2.0f, q, w);
+    return inl;
+}
+
+// the last kernel argument of a sigma-consensus finish kernel is `float* quality`; the hard-count instance has none
+__device__ __forceinline__ void store_quality(int, float) {}
+__device__ __forceinline__ void store_quality(int b, float v, float* quality) { quality[b] = v; }
 
 // symmetric 3 x 3 eigen-decomposition by cyclic Jacobi: A = V diag(A) V^T on return
 __device__ inline void jacobi3(double (&A)[3][3], double (&V)[3][3]) {

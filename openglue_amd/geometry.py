@@ -13,13 +13,26 @@ normalised eight-point refits on the inliers, each kept if it loses no inlier.  
 calls of one pair with pair_offset = b give what one batched call gives.
 
 Where this deliberately differs from cv2.USAC_MAGSAC:
-  * no sigma-consensus scoring: `threshold` is a plain inlier threshold on the Sampson error;
+  * the default scoring="inliers" counts: `threshold` is a plain inlier threshold on the Sampson error.  scoring="sigma" reproduces
+    MAGSAC++'s sigma-consensus scoring and its weighted refit (below); USAC's adaptive stop, its local-optimisation schedule and its
+    degeneracy test are still not reproduced;
   * the sample count is fixed: every one of `hypotheses` samples is evaluated, there is no adaptive stop (2048 gives 0.999
     confidence down to an inlier ratio of about 0.45: ln 0.001 / ln(1 - 0.45^7) ~ 1850);
   * the random draws are the hash's, not OpenCV's generator;
   * there is no degeneracy test for planar scenes or dominant planes: for such input F is whatever the data support (a homography
     leaves a family of F that fit equally well), and the mask is still finite and deterministic.
 With fewer than 7 valid matches, or no surviving model, F is zero, no match is an inlier and best_model is -1 (cv2 returns None).
+
+scoring="sigma" (fundamental_matrix, find_fundamental, homography, find_homography; og_fundamental_matrix_sc / og_homography_sc,
+csrc/sigma_consensus.hip) marginalises over the noise scale up to sigma_max = threshold / 3.64, with OpenCV's constants (4 degrees of
+freedom, a = 1.5, u_max = 3.64^2 / 2).  With e a match's squared residual, t = e / threshold^2 and u = t u_max:
+  w(t) = (G(a, u) - G(a, u_max)) / (G(a) - G(a, u_max)),   q(t) = 1 - (g(a + 1, u) + u (G(a, u) - G(a, u_max))) / g(a + 1, u_max)
+for t <= 1 (G / g: upper / lower incomplete gamma), 0 otherwise.  A model's score is Q = sum of rint(65536 q(t)) over the valid
+matches, an integer, so the winner is independent of the summation order; the refits weigh each match's rows by w(t) and are kept
+when Q does not drop; 'inliers' and 'num_inliers' keep their meaning (e <= threshold^2 under the final model) and 'quality' is
+Q / 65536, the soft inlier count.  `threshold` is then an upper bound on the noise rather than a decision boundary: a generous one
+costs little (8 px where the noise is 0.5 px loses nothing), one below about twice the noise makes the weights too tight and is
+worse than counting (DESIGN 4.10c has the figures).  sigma_consensus(t) evaluates q and w as the kernels do.
 
 Planar scenes, and the pairs of the homography pre-training stage, get the same treatment with the homography as the model
 (cv2.findHomography(keypoints0, keypoints1, cv2.RANSAC, 3.0)):
@@ -55,12 +68,24 @@ def _shape(t, name: str) -> Tuple[int, ...]:
     return tuple(t.shape)
 
 
+SIGMA_MAX_MATCHES = 32768      # og_fundamental_matrix_sc / og_homography_sc: Q + 1 must fit 32 bits
+
+
+def _sigma(scoring) -> bool:
+    """scoring -> whether it is "sigma"; anything but "inliers" and "sigma" is refused before any device work."""
+    if scoring not in ("inliers", "sigma"):
+        raise ValueError(f"scoring must be 'inliers' or 'sigma', got {scoring!r}")
+    return scoring == "sigma"
+
+
 def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold: float = 1.0, hypotheses: int = 2048,
-                       refine: int = 2, seed: int = 0, pair_offset: int = 0) -> Dict[str, torch.Tensor]:
+                       refine: int = 2, seed: int = 0, pair_offset: int = 0, scoring: str = "inliers") -> Dict[str, torch.Tensor]:
     """keypoints0 [B, M, 2], keypoints1 [B, N, 2] (pixels), matches0 [B, M] (-1 or outside [0, N): no match), num_keypoints0 [B]
     (None: M) -> {'F' [B, 3, 3] float64 in pixels with x1^T F x0 = 0, unit Frobenius norm, largest entry positive; 'inliers' [B, M]
     bool at the positions of keypoints0; 'num_inliers' [B] int32; 'best_model' [B] int32 = hypothesis * 3 + solution of the RANSAC
-    winner, -1 without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is)."""
+    winner, -1 without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is).  scoring="sigma":
+    sigma-consensus scoring and weighted refits (module docstring), M <= 32768, and 'quality' [B] float32 joins the dict."""
+    sigma = _sigma(scoring)
     s0, s1, sm = _shape(keypoints0, "keypoints0"), _shape(keypoints1, "keypoints1"), _shape(matches0, "matches0")
     if len(s0) != 3 or s0[2] != 2 or len(s1) != 3 or s1[2] != 2 or s1[0] != s0[0] or s0[0] == 0:
         raise ValueError(f"keypoints0 / keypoints1 must be [B, M, 2] / [B, N, 2] with B > 0, got {list(s0)} / {list(s1)}")
@@ -74,6 +99,8 @@ def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, th
         raise ValueError(f"hypotheses must be positive, refine and threshold non-negative, got {hypotheses}, {refine}, {threshold}")
     if 3 * B * hypotheses > 2 ** 30:
         raise ValueError(f"3 * batch * hypotheses must not exceed 2^30, got 3 * {B} * {hypotheses}")
+    if sigma and M > SIGMA_MAX_MATCHES:
+        raise ValueError(f"scoring='sigma' takes at most {SIGMA_MAX_MATCHES} keypoints per image, got M = {M}")
     k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
     k1 = _lib.gpu_tensor(keypoints1, "keypoints1", convert=True)
     m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
@@ -84,6 +111,12 @@ def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, th
     inl = torch.empty(B, max(M, 1), device=dev, dtype=torch.uint8)
     ninl = torch.empty(B, device=dev, dtype=torch.int32)
     best = torch.empty(B, device=dev, dtype=torch.int32)
+    if sigma:
+        quality = torch.empty(B, device=dev, dtype=torch.float32)
+        _lib.call("og_fundamental_matrix_sc", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
+                  hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), F.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
+                  best.data_ptr(), quality.data_ptr(), wp, _lib.STREAM)
+        return {"F": F, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best, "quality": quality}
     _lib.call("og_fundamental_matrix", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
               hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), F.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
               best.data_ptr(), wp, _lib.STREAM)
@@ -92,7 +125,8 @@ def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, th
 
 def find_fundamental(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
     """One pair as inference.py passes it to cv2.findFundamentalMat: matched keypoints [K, 2] of both images -> (F [3, 3] float64,
-    inliers [K] bool).  Keyword arguments as fundamental_matrix (threshold, hypotheses, refine, seed, pair_offset)."""
+    inliers [K] bool).  Keyword arguments as fundamental_matrix (threshold, hypotheses, refine, seed, pair_offset, scoring)."""
+    _sigma(kw.get("scoring", "inliers"))
     s0, s1 = _shape(matched_kpts0, "matched_kpts0"), _shape(matched_kpts1, "matched_kpts1")
     if len(s0) != 2 or s0[1] != 2 or s1 != s0:
         raise ValueError(f"matched_kpts0 / matched_kpts1 must both be [K, 2], got {list(s0)} / {list(s1)}")
@@ -120,11 +154,13 @@ def fundamental_7pt(x0: torch.Tensor, x1: torch.Tensor):
 
 
 def homography(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold: float = 3.0, hypotheses: int = 2048,
-               refine: int = 2, seed: int = 0, pair_offset: int = 0) -> Dict[str, torch.Tensor]:
+               refine: int = 2, seed: int = 0, pair_offset: int = 0, scoring: str = "inliers") -> Dict[str, torch.Tensor]:
     """keypoints0 [B, M, 2], keypoints1 [B, N, 2] (pixels), matches0 [B, M] (-1 or outside [0, N): no match), num_keypoints0 [B]
     (None: M) -> {'H' [B, 3, 3] float64 in pixels with x1 ~ H x0, unit Frobenius norm, largest entry positive; 'inliers' [B, M]
     bool at the positions of keypoints0; 'num_inliers' [B] int32; 'best_model' [B] int32 = hypothesis of the RANSAC winner, -1
-    without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is)."""
+    without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is).  scoring="sigma":
+    sigma-consensus scoring and weighted refits (module docstring), M <= 32768, and 'quality' [B] float32 joins the dict."""
+    sigma = _sigma(scoring)
     s0, s1, sm = _shape(keypoints0, "keypoints0"), _shape(keypoints1, "keypoints1"), _shape(matches0, "matches0")
     if len(s0) != 3 or s0[2] != 2 or len(s1) != 3 or s1[2] != 2 or s1[0] != s0[0] or s0[0] == 0:
         raise ValueError(f"keypoints0 / keypoints1 must be [B, M, 2] / [B, N, 2] with B > 0, got {list(s0)} / {list(s1)}")
@@ -138,6 +174,8 @@ def homography(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold:
         raise ValueError(f"hypotheses must be positive, refine and threshold non-negative, got {hypotheses}, {refine}, {threshold}")
     if B * hypotheses > 2 ** 30:
         raise ValueError(f"batch * hypotheses must not exceed 2^30, got {B} * {hypotheses}")
+    if sigma and M > SIGMA_MAX_MATCHES:
+        raise ValueError(f"scoring='sigma' takes at most {SIGMA_MAX_MATCHES} keypoints per image, got M = {M}")
     k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
     k1 = _lib.gpu_tensor(keypoints1, "keypoints1", convert=True)
     m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
@@ -148,6 +186,12 @@ def homography(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold:
     inl = torch.empty(B, max(M, 1), device=dev, dtype=torch.uint8)
     ninl = torch.empty(B, device=dev, dtype=torch.int32)
     best = torch.empty(B, device=dev, dtype=torch.int32)
+    if sigma:
+        quality = torch.empty(B, device=dev, dtype=torch.float32)
+        _lib.call("og_homography_sc", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
+                  hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), H.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
+                  best.data_ptr(), quality.data_ptr(), wp, _lib.STREAM)
+        return {"H": H, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best, "quality": quality}
     _lib.call("og_homography", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
               hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), H.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
               best.data_ptr(), wp, _lib.STREAM)
@@ -157,7 +201,8 @@ def homography(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold:
 def find_homography(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
     """One pair as a caller passes it to cv2.findHomography: matched keypoints [K, 2] of both images -> (H [3, 3] float64 divided by
     H[2, 2] as cv2 returns it, zero without a model; inliers [K] bool).  Keyword arguments as homography (threshold, hypotheses,
-    refine, seed, pair_offset).  An H whose last entry is 0 (the origin sent to infinity) has no such form and comes out non-finite."""
+    refine, seed, pair_offset, scoring).  An H whose last entry is 0 (the origin sent to infinity) has no such form and comes out non-finite."""
+    _sigma(kw.get("scoring", "inliers"))
     s0, s1 = _shape(matched_kpts0, "matched_kpts0"), _shape(matched_kpts1, "matched_kpts1")
     if len(s0) != 2 or s0[1] != 2 or s1 != s0:
         raise ValueError(f"matched_kpts0 / matched_kpts1 must both be [K, 2], got {list(s0)} / {list(s1)}")
@@ -184,3 +229,20 @@ def homography_4pt(x0: torch.Tensor, x1: torch.Tensor):
     ns = torch.empty(count, device=dev, dtype=torch.int32)
     _lib.call("og_homography_4pt", dev, count, a.data_ptr(), b.data_ptr(), H.data_ptr(), ns.data_ptr(), _lib.STREAM)
     return H, ns
+
+
+def sigma_consensus(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The sigma-consensus quality and weight as the kernels evaluate them (og_sigma_consensus_eval): t = e / threshold^2, any shape,
+    float32 -> (q int64 in units of 2^-16, i.e. rint(65536 q(t)) within one unit and non-increasing in t; w float32).  Both are 0 for
+    t outside [0, 1] and for NaN; t = 0 gives (65536, 1)."""
+    shape = _shape(t, "t")
+    count = 1
+    for d in shape:
+        count *= d
+    if not 0 < count <= 2 ** 30:
+        raise ValueError(f"t must hold between 1 and 2^30 values, got {list(shape)}")
+    a = _lib.gpu_tensor(t, "t", convert=True)
+    q = torch.empty(count, device=a.device, dtype=torch.int32)
+    w = torch.empty(count, device=a.device, dtype=torch.float32)
+    _lib.call("og_sigma_consensus_eval", a.device, count, a.data_ptr(), q.data_ptr(), w.data_ptr(), _lib.STREAM)
+    return q.to(torch.int64).reshape(shape), w.reshape(shape)
