@@ -625,8 +625,8 @@ int og_homography_precision(int32_t batch, int32_t m, int32_t n, const float* ke
 int og_homography_corner_error(int32_t batch, const double* H_est, const float* H_true, int32_t width, int32_t height, float* error,
                                void* stream);
 
-/* Sigma-consensus scoring (MAGSAC++, what cv2.USAC_MAGSAC scores with) for the two estimators above (csrc/sigma_consensus.hip over
- * the kernels of geometry.hip / homography.hip).  Added to ABI v14 without a version bump: three new entries, nothing existing
+/* Sigma-consensus scoring (MAGSAC++, what cv2.USAC_MAGSAC scores with) for the two estimators above (the _sc entries in csrc/geometry.hip
+ * and csrc/homography.hip, og_sigma_consensus_eval in csrc/sigma_consensus.hip).  Added to ABI v14 without a version bump: three new entries, nothing existing
  * changes.  Constants as OpenCV's: 4 degrees of freedom, a = 1.5, k = 3.64, sigma_max = threshold / k, u_max = k^2 / 2.  With e a
  * match's squared residual (pixels^2: Sampson for F, forward transfer for H), t = e / threshold^2 and u = t u_max,
  *   w(t) = (G(a, u) - G(a, u_max)) / (G(a) - G(a, u_max)),   q(t) = 1 - (g(a + 1, u) + u (G(a, u) - G(a, u_max))) / g(a + 1, u_max)

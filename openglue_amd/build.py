@@ -37,7 +37,6 @@ def _hipcc() -> str:
 # live on packed fp32, keep it).  The host pass does not know the feature and says so; harmless.
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 PER_FILE_FLAGS = {"attention.hip": _NO_PACKED_FP32}
-INCLUDES = {"sigma_consensus.hip": ["geometry.hip", "homography.hip"]}      # units a source includes: it is stale when they are newer
 FLAGS = ["--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-O3", "-Wall", "-Wno-unused-function"]      # every source; PER_FILE_FLAGS add to these
 
 
@@ -60,7 +59,7 @@ def build(force: bool = False, debug: bool = False, verbose: bool = True) -> str
         sp = os.path.join(CSRC, src)
         op = os.path.join(LIB_DIR, src.replace(".hip", ".o"))
         objs.append(op)
-        if force or _stale(op, [sp, *(os.path.join(CSRC, i) for i in INCLUDES.get(src, [])), *headers, os.path.abspath(__file__)]):
+        if force or _stale(op, [sp, *headers, os.path.abspath(__file__)]):
             jobs.append([hipcc, *flags, *PER_FILE_FLAGS.get(src, []), "-c", sp, "-o", op])
 
     def run(cmd):

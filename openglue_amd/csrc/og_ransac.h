@@ -1,6 +1,8 @@
-// Helpers the RANSAC units share (metrics.hip: five-point / essential matrix, geometry.hip: seven-point / fundamental matrix,
-// homography.hip: four-point / homography).
-// Internal, not part of the ABI.  Everything lives in the unnamed namespace of the including unit, as it did in metrics.hip.
+// Helpers every RANSAC unit shares (metrics.hip: five-point / essential matrix; geometry.hip: seven-point / fundamental matrix and
+// homography.hip: four-point / homography, both through og_ransac_hartley.h, which includes this file and holds their common skeleton;
+// sigma_consensus.hip: the sigma-consensus table on its own): the polynomial helpers, the counter-based draws, the validity rule and
+// compaction of matches, the packed winner, sigma-consensus q and w, and jacobi3.
+// Internal, not part of the ABI.  Everything lives in the unnamed namespace of the including unit.
 // The workgroup sum and the compaction rank come from og_block.h.
 #pragma once
 #include "og_block.h"
@@ -54,7 +56,7 @@ __host__ __device__ inline void draw_distinct(uint64_t seed, uint64_t pair, int 
     }
 }
 
-// The validity rule of both units: keypoint i of pair b is matched when i < num_keypoints0[b] and 0 <= matches0[i] < n.  G carries
+// The validity rule of every unit: keypoint i of pair b is matched when i < num_keypoints0[b] and 0 <= matches0[i] < n.  G carries
 // matches0 [B][m] int64, nk0 [B] (or null: m), m and n.
 template <class G>
 __device__ inline bool valid_match(const G& g, int b, int i, int& j) {
@@ -86,7 +88,7 @@ __device__ inline int compact_valid_matches(const G& g, int b, int* idx, int* ws
 
 __device__ __forceinline__ float4 to_f4(double4 d) { return make_float4((float)d.x, (float)d.y, (float)d.z, (float)d.w); }
 
-// The tail of both score kernels: a thread's key is (inliers + 1) << 32 | ~model, 0 for "no model"; the wave's largest goes into
+// The tail of the score kernels: a thread's key is (inliers + 1) << 32 | ~model, 0 for "no model"; the wave's largest goes into
 // the pair's winner by one 64-bit atomicMax (more inliers win, then the lower model index).
 __device__ __forceinline__ void publish_best(unsigned long long key, unsigned long long* best) {
 #pragma unroll
@@ -191,101 +193,6 @@ __device__ inline void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
                 V[k][q] = s * vkp + c * vkq;
             }
         }
-    }
-}
-
-// The prep kernel of the Hartley-normalised units (geometry.hip, homography.hip), one workgroup of 256 per pair: the valid matches
-// compacted in index order, both images normalised in fp64 (centroid, mean distance sqrt 2) with every sum over the COMPACTED order
-// lanes-then-waves, and the pair's winner reset.  W carries pts [B][m] double4 (u0, v0, u1, v1), idx [B][m], count [B],
-// norm [B][6] (centroid and scale of image 0, of image 1) and best [B].
-template <class G, class W>
-__device__ inline void hartley_prep_pair(const G& g, const W& w) {
-    __shared__ int wsum[4];
-    __shared__ double red[4];
-    const int b = blockIdx.x;
-    const int n = compact_valid_matches(g, b, w.idx + (int64_t)b * g.m, wsum, [](int, int) {});      // the rule and order of metrics.hip
-    // pixel coordinates of compacted match k (idx was written by this workgroup before the last barrier of the compaction)
-    auto pixel = [&](int k) {
-        const int i = w.idx[(int64_t)b * g.m + k];
-        const int j = (int)g.matches0[(int64_t)b * g.m + i];
-        const float2 a = ((const float2*)g.k0)[(int64_t)b * g.m + i];
-        const float2 c = ((const float2*)g.k1)[(int64_t)b * g.n + j];
-        return make_double4((double)a.x, (double)a.y, (double)c.x, (double)c.y);
-    };
-    double s[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const double4 q = pixel(k);
-        s[0] += q.x; s[1] += q.y; s[2] += q.z; s[3] += q.w;
-    }
-    const double inv_n = n > 0 ? 1.0 / (double)n : 0.0;
-    double cen[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) cen[c] = block_sum(s[c], red) * inv_n;
-    double d[2] = {0.0, 0.0};
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const double4 q = pixel(k);
-        d[0] += sqrt((q.x - cen[0]) * (q.x - cen[0]) + (q.y - cen[1]) * (q.y - cen[1]));
-        d[1] += sqrt((q.z - cen[2]) * (q.z - cen[2]) + (q.w - cen[3]) * (q.w - cen[3]));
-    }
-    double sc[2];
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const double mean = block_sum(d[c], red) * inv_n;
-        const double v = M_SQRT2 / mean;
-        sc[c] = (mean > 0.0 && finite(v)) ? v : 1.0;              // every point on the centroid: leave the scale alone
-    }
-    for (int k = threadIdx.x; k < n; k += 256) {
-        const double4 q = pixel(k);
-        w.pts[(int64_t)b * g.m + k] = make_double4(sc[0] * (q.x - cen[0]), sc[0] * (q.y - cen[1]), sc[1] * (q.z - cen[2]), sc[1] * (q.w - cen[3]));
-    }
-    if (threadIdx.x == 0) {
-        double* o = w.norm + (int64_t)b * 6;
-        o[0] = cen[0]; o[1] = cen[1]; o[2] = sc[0]; o[3] = cen[2]; o[4] = cen[3]; o[5] = sc[1];
-        w.count[b] = n;
-        w.best[b] = 0ull;
-    }
-}
-
-// index of (i, j) among the 45 distinct entries of a symmetric 9 x 9 matrix, rows of the upper triangle one after the other
-__host__ __device__ constexpr int tri(int i, int j) { return i <= j ? i * 9 - i * (i - 1) / 2 + (j - i) : j * 9 - j * (j - 1) / 2 + (i - j); }
-
-// Symmetric 9 x 9 eigen-decomposition by cyclic Jacobi, the form of jacobi3 spread over one wave: lane k < 9 holds row k of A (a) and
-// row k of V (v); the other lanes carry zeros along.  A rotation (p, q) updates columns p, q of A and V inside every lane, and rows
-// p, q of A in the lanes p and q, which read each other's row.  All 64 lanes must call it.  On return a[k] of lane k is eigenvalue k
-// and column k of V its eigenvector.
-__device__ inline void jacobi9_wave(double (&a)[9], double (&v)[9], int lane) {
-#pragma unroll
-    for (int j = 0; j < 9; ++j) v[j] = lane == j ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 16; ++sweep) {
-        double off = 0.0, dia = 0.0;
-#pragma unroll
-        for (int j = 0; j < 9; ++j) { off += lane == j ? 0.0 : a[j] * a[j]; dia += lane == j ? a[j] * a[j] : 0.0; }
-#pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { off += __shfl_xor(off, o, 64); dia += __shfl_xor(dia, o, 64); }
-        off = __shfl(off, 0, 64); dia = __shfl(dia, 0, 64);
-        if (!(off > 1e-34 * dia)) break;
-#pragma unroll
-        for (int p = 0; p < 8; ++p)
-#pragma unroll
-            for (int q = p + 1; q < 9; ++q) {
-                const double app = __shfl(a[p], p, 64), aqq = __shfl(a[q], q, 64), apq = __shfl(a[q], p, 64);
-                const bool rot = fabs(apq) >= 1e-300;
-                const double theta = (aqq - app) / (2.0 * (rot ? apq : 1.0));
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = rot ? 1.0 / sqrt(t * t + 1.0) : 1.0, s = rot ? t * c : 0.0;
-                // A <- J^T A J, V <- V J with J_pp = J_qq = c, J_pq = s, J_qp = -s
-                const double akp = a[p], akq = a[q];
-                a[p] = c * akp - s * akq;
-                a[q] = s * akp + c * akq;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) {
-                    const double apk = __shfl(a[k], p, 64), aqk = __shfl(a[k], q, 64);
-                    a[k] = lane == p ? c * apk - s * aqk : lane == q ? s * apk + c * aqk : a[k];
-                }
-                const double vkp = v[p], vkq = v[q];
-                v[p] = c * vkp - s * vkq;
-                v[q] = s * vkp + c * vkq;
-            }
     }
 }
 

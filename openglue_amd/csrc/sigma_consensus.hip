@@ -1,17 +1,15 @@
 // Sigma-consensus (MAGSAC++) scoring and weighted refits for the fundamental-matrix and homography RANSAC: what cv2.USAC_MAGSAC
-// scores with, on the kernels of geometry.hip and homography.hip.
+// scores with.
 //
-//  * og_fundamental_matrix_sc / og_homography_sc -- the four launches of og_fundamental_matrix / og_homography with the SC = 1
-//    instances of the score and finish kernels: a model's score is Q = sum over its matches of rint(65536 q(e / threshold^2)), the
-//    winner the largest Q (lowest model on ties, the same packed atomicMax), the refits are least squares weighted by w and kept when Q
-//    does not drop, and `quality` is Q / 65536 of the final model.  The kernel templates and the two entries are in geometry.hip and
-//    homography.hip, which this unit includes with OG_SIGMA_UNIT set: those units keep exactly the kernels they had, this one
-//    holds the sigma-consensus instances.  q, w and the per-match rule are og_ransac.h's (sigma_consensus, sigma_match).
+//  * og_fundamental_matrix_sc / og_homography_sc are in geometry.hip / homography.hip: the four launches of og_fundamental_matrix /
+//    og_homography with the SC = 1 instances of og_ransac_hartley.h's score and finish kernels.  A model's score is Q = sum over its
+//    matches of rint(65536 q(e / threshold^2)), the winner the largest Q (lowest model on ties, the same packed atomicMax), the refits
+//    are least squares weighted by w and kept when Q does not drop, and `quality` is Q / 65536 of the final model.  q, w and the
+//    per-match rule are og_ransac.h's (sigma_consensus, sigma_match).
 //
-//  * og_sigma_consensus_eval -- sigma_eval_kernel: sigma_consensus over an array of t.
-#define OG_SIGMA_UNIT 1
-#include "geometry.hip"
-#include "homography.hip"
+//  * og_sigma_consensus_eval -- sigma_eval_kernel: sigma_consensus over an array of t, as those kernels evaluate it.
+#include "og_common.h"
+#include "og_ransac.h"
 
 namespace {
 

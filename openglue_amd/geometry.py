@@ -24,7 +24,7 @@ Where this deliberately differs from cv2.USAC_MAGSAC:
 With fewer than 7 valid matches, or no surviving model, F is zero, no match is an inlier and best_model is -1 (cv2 returns None).
 
 scoring="sigma" (fundamental_matrix, find_fundamental, homography, find_homography; og_fundamental_matrix_sc / og_homography_sc,
-csrc/sigma_consensus.hip) marginalises over the noise scale up to sigma_max = threshold / 3.64, with OpenCV's constants (4 degrees of
+in the same two units) marginalises over the noise scale up to sigma_max = threshold / 3.64, with OpenCV's constants (4 degrees of
 freedom, a = 1.5, u_max = 3.64^2 / 2).  With e a match's squared residual, t = e / threshold^2 and u = t u_max:
   w(t) = (G(a, u) - G(a, u_max)) / (G(a) - G(a, u_max)),   q(t) = 1 - (g(a + 1, u) + u (G(a, u) - G(a, u_max))) / g(a + 1, u_max)
 for t <= 1 (G / g: upper / lower incomplete gamma), 0 otherwise.  A model's score is Q = sum of rint(65536 q(t)) over the valid
@@ -78,13 +78,10 @@ def _sigma(scoring) -> bool:
     return scoring == "sigma"
 
 
-def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold: float = 1.0, hypotheses: int = 2048,
-                       refine: int = 2, seed: int = 0, pair_offset: int = 0, scoring: str = "inliers") -> Dict[str, torch.Tensor]:
-    """keypoints0 [B, M, 2], keypoints1 [B, N, 2] (pixels), matches0 [B, M] (-1 or outside [0, N): no match), num_keypoints0 [B]
-    (None: M) -> {'F' [B, 3, 3] float64 in pixels with x1^T F x0 = 0, unit Frobenius norm, largest entry positive; 'inliers' [B, M]
-    bool at the positions of keypoints0; 'num_inliers' [B] int32; 'best_model' [B] int32 = hypothesis * 3 + solution of the RANSAC
-    winner, -1 without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is).  scoring="sigma":
-    sigma-consensus scoring and weighted refits (module docstring), M <= 32768, and 'quality' [B] float32 joins the dict."""
+def _ransac(key, entry, ws_entry, models, keypoints0, keypoints1, matches0, num_keypoints0, threshold, hypotheses, refine, seed, pair_offset,
+            scoring) -> Dict[str, torch.Tensor]:
+    """The batched call of fundamental_matrix (key "F", 3 models per sample) and homography (key "H", 1): the checks, the workspace of
+    `ws_entry`, and `entry` or, with scoring="sigma", `entry`_sc, which takes `quality` as well."""
     sigma = _sigma(scoring)
     s0, s1, sm = _shape(keypoints0, "keypoints0"), _shape(keypoints1, "keypoints1"), _shape(matches0, "matches0")
     if len(s0) != 3 or s0[2] != 2 or len(s1) != 3 or s1[2] != 2 or s1[0] != s0[0] or s0[0] == 0:
@@ -97,8 +94,9 @@ def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, th
     hypotheses, refine = int(hypotheses), int(refine)
     if hypotheses <= 0 or refine < 0 or not float(threshold) >= 0.0:
         raise ValueError(f"hypotheses must be positive, refine and threshold non-negative, got {hypotheses}, {refine}, {threshold}")
-    if 3 * B * hypotheses > 2 ** 30:
-        raise ValueError(f"3 * batch * hypotheses must not exceed 2^30, got 3 * {B} * {hypotheses}")
+    if models * B * hypotheses > 2 ** 30:
+        per = f"{models} * " if models > 1 else ""
+        raise ValueError(f"{per}batch * hypotheses must not exceed 2^30, got {per}{B} * {hypotheses}")
     if sigma and M > SIGMA_MAX_MATCHES:
         raise ValueError(f"scoring='sigma' takes at most {SIGMA_MAX_MATCHES} keypoints per image, got M = {M}")
     k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
@@ -106,26 +104,23 @@ def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, th
     m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
     nk = None if num_keypoints0 is None else _lib.gpu_tensor(num_keypoints0, "num_keypoints0", torch.int32, convert=True)
     dev = k0.device
-    ws, wp = _lib.workspace(_lib.load().og_fundamental_matrix_workspace_bytes(B, M, hypotheses), dev)      # sizes checked above
-    F = torch.empty(B, 3, 3, device=dev, dtype=torch.float64)
+    ws, wp = _lib.workspace(getattr(_lib.load(), ws_entry)(B, M, hypotheses), dev)      # sizes checked above
+    model = torch.empty(B, 3, 3, device=dev, dtype=torch.float64)
     inl = torch.empty(B, max(M, 1), device=dev, dtype=torch.uint8)
     ninl = torch.empty(B, device=dev, dtype=torch.int32)
     best = torch.empty(B, device=dev, dtype=torch.int32)
+    r = {key: model, "inliers": inl, "num_inliers": ninl, "best_model": best}
     if sigma:
-        quality = torch.empty(B, device=dev, dtype=torch.float32)
-        _lib.call("og_fundamental_matrix_sc", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
-                  hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), F.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
-                  best.data_ptr(), quality.data_ptr(), wp, _lib.STREAM)
-        return {"F": F, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best, "quality": quality}
-    _lib.call("og_fundamental_matrix", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
-              hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), F.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
-              best.data_ptr(), wp, _lib.STREAM)
-    return {"F": F, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best}
+        r["quality"] = torch.empty(B, device=dev, dtype=torch.float32)
+    _lib.call(entry + "_sc" if sigma else entry, dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
+              hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), model.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
+              best.data_ptr(), *([r["quality"].data_ptr()] if sigma else []), wp, _lib.STREAM)
+    r["inliers"] = inl[:, :M].bool()
+    return r
 
 
-def find_fundamental(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
-    """One pair as inference.py passes it to cv2.findFundamentalMat: matched keypoints [K, 2] of both images -> (F [3, 3] float64,
-    inliers [K] bool).  Keyword arguments as fundamental_matrix (threshold, hypotheses, refine, seed, pair_offset, scoring)."""
+def _find(batched, matched_kpts0, matched_kpts1, kw) -> Dict[str, torch.Tensor]:
+    """One pair of compacted matches [K, 2] / [K, 2] through `batched` (fundamental_matrix or homography) as a batch of one."""
     _sigma(kw.get("scoring", "inliers"))
     s0, s1 = _shape(matched_kpts0, "matched_kpts0"), _shape(matched_kpts1, "matched_kpts1")
     if len(s0) != 2 or s0[1] != 2 or s1 != s0:
@@ -133,24 +128,46 @@ def find_fundamental(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, 
     k0 = _lib.gpu_tensor(matched_kpts0, "matched_kpts0", convert=True)
     k1 = _lib.gpu_tensor(matched_kpts1, "matched_kpts1", convert=True)
     m0 = torch.arange(k0.shape[0], device=k0.device).unsqueeze(0)
-    r = fundamental_matrix(k0.unsqueeze(0), k1.unsqueeze(0), m0, **kw)
+    return batched(k0.unsqueeze(0), k1.unsqueeze(0), m0, **kw)
+
+
+def _minimal(entry, sample, models, x0, x1):
+    """A minimal solver on its own: x0, x1 [count, sample, 2] -> (models [count, (models,) 3, 3] float64, num_solutions [count] int32)."""
+    s0, s1 = _shape(x0, "x0"), _shape(x1, "x1")
+    if len(s0) != 3 or s0[1:] != (sample, 2) or s1 != s0 or not 0 < s0[0] <= 2 ** 30:
+        raise ValueError(f"x0 / x1 must both be [count, {sample}, 2] with 0 < count <= 2^30, got {list(s0)} / {list(s1)}")
+    a = _lib.gpu_tensor(x0, "x0", torch.float64, convert=True)
+    b = _lib.gpu_tensor(x1, "x1", torch.float64, convert=True)
+    count = a.shape[0]
+    dev = a.device
+    out = torch.empty(count, *([models] if models > 1 else []), 3, 3, device=dev, dtype=torch.float64)
+    ns = torch.empty(count, device=dev, dtype=torch.int32)
+    _lib.call(entry, dev, count, a.data_ptr(), b.data_ptr(), out.data_ptr(), ns.data_ptr(), _lib.STREAM)
+    return out, ns
+
+
+def fundamental_matrix(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold: float = 1.0, hypotheses: int = 2048,
+                       refine: int = 2, seed: int = 0, pair_offset: int = 0, scoring: str = "inliers") -> Dict[str, torch.Tensor]:
+    """keypoints0 [B, M, 2], keypoints1 [B, N, 2] (pixels), matches0 [B, M] (-1 or outside [0, N): no match), num_keypoints0 [B]
+    (None: M) -> {'F' [B, 3, 3] float64 in pixels with x1^T F x0 = 0, unit Frobenius norm, largest entry positive; 'inliers' [B, M]
+    bool at the positions of keypoints0; 'num_inliers' [B] int32; 'best_model' [B] int32 = hypothesis * 3 + solution of the RANSAC
+    winner, -1 without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is).  scoring="sigma":
+    sigma-consensus scoring and weighted refits (module docstring), M <= 32768, and 'quality' [B] float32 joins the dict."""
+    return _ransac("F", "og_fundamental_matrix", "og_fundamental_matrix_workspace_bytes", 3, keypoints0, keypoints1, matches0, num_keypoints0,
+                   threshold, hypotheses, refine, seed, pair_offset, scoring)
+
+
+def find_fundamental(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One pair as inference.py passes it to cv2.findFundamentalMat: matched keypoints [K, 2] of both images -> (F [3, 3] float64,
+    inliers [K] bool).  Keyword arguments as fundamental_matrix (threshold, hypotheses, refine, seed, pair_offset, scoring)."""
+    r = _find(fundamental_matrix, matched_kpts0, matched_kpts1, kw)
     return r["F"][0], r["inliers"][0]
 
 
 def fundamental_7pt(x0: torch.Tensor, x1: torch.Tensor):
     """The seven-point minimal solver on its own: x0, x1 [count, 7, 2] correspondences (x1^T F x0 = 0) with coordinates of order 1
     -> (F [count, 3, 3, 3] float64, unit Frobenius norm, zero past num_solutions; num_solutions [count] int32, 0..3)."""
-    s0, s1 = _shape(x0, "x0"), _shape(x1, "x1")
-    if len(s0) != 3 or s0[1:] != (7, 2) or s1 != s0 or not 0 < s0[0] <= 2 ** 30:
-        raise ValueError(f"x0 / x1 must both be [count, 7, 2] with 0 < count <= 2^30, got {list(s0)} / {list(s1)}")
-    a = _lib.gpu_tensor(x0, "x0", torch.float64, convert=True)
-    b = _lib.gpu_tensor(x1, "x1", torch.float64, convert=True)
-    count = a.shape[0]
-    dev = a.device
-    F = torch.empty(count, 3, 3, 3, device=dev, dtype=torch.float64)
-    ns = torch.empty(count, device=dev, dtype=torch.int32)
-    _lib.call("og_fundamental_7pt", dev, count, a.data_ptr(), b.data_ptr(), F.data_ptr(), ns.data_ptr(), _lib.STREAM)
-    return F, ns
+    return _minimal("og_fundamental_7pt", 7, 3, x0, x1)
 
 
 def homography(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold: float = 3.0, hypotheses: int = 2048,
@@ -160,56 +177,15 @@ def homography(keypoints0, keypoints1, matches0, num_keypoints0=None, threshold:
     bool at the positions of keypoints0; 'num_inliers' [B] int32; 'best_model' [B] int32 = hypothesis of the RANSAC winner, -1
     without one}.  `threshold` in pixels; `refine` least-squares rounds (0: the minimal model as it is).  scoring="sigma":
     sigma-consensus scoring and weighted refits (module docstring), M <= 32768, and 'quality' [B] float32 joins the dict."""
-    sigma = _sigma(scoring)
-    s0, s1, sm = _shape(keypoints0, "keypoints0"), _shape(keypoints1, "keypoints1"), _shape(matches0, "matches0")
-    if len(s0) != 3 or s0[2] != 2 or len(s1) != 3 or s1[2] != 2 or s1[0] != s0[0] or s0[0] == 0:
-        raise ValueError(f"keypoints0 / keypoints1 must be [B, M, 2] / [B, N, 2] with B > 0, got {list(s0)} / {list(s1)}")
-    B, M, N = s0[0], s0[1], s1[1]
-    if sm != (B, M):
-        raise ValueError(f"matches0 must be [B, M] = [{B}, {M}], got {list(sm)}")
-    if num_keypoints0 is not None and _shape(num_keypoints0, "num_keypoints0") != (B,):
-        raise ValueError(f"num_keypoints0 must be [B] = [{B}], got {list(num_keypoints0.shape)}")
-    hypotheses, refine = int(hypotheses), int(refine)
-    if hypotheses <= 0 or refine < 0 or not float(threshold) >= 0.0:
-        raise ValueError(f"hypotheses must be positive, refine and threshold non-negative, got {hypotheses}, {refine}, {threshold}")
-    if B * hypotheses > 2 ** 30:
-        raise ValueError(f"batch * hypotheses must not exceed 2^30, got {B} * {hypotheses}")
-    if sigma and M > SIGMA_MAX_MATCHES:
-        raise ValueError(f"scoring='sigma' takes at most {SIGMA_MAX_MATCHES} keypoints per image, got M = {M}")
-    k0 = _lib.gpu_tensor(keypoints0, "keypoints0", convert=True)
-    k1 = _lib.gpu_tensor(keypoints1, "keypoints1", convert=True)
-    m0 = _lib.gpu_tensor(matches0, "matches0", torch.int64, convert=True)
-    nk = None if num_keypoints0 is None else _lib.gpu_tensor(num_keypoints0, "num_keypoints0", torch.int32, convert=True)
-    dev = k0.device
-    ws, wp = _lib.workspace(_lib.load().og_homography_workspace_bytes(B, M, hypotheses), dev)      # sizes checked above
-    H = torch.empty(B, 3, 3, device=dev, dtype=torch.float64)
-    inl = torch.empty(B, max(M, 1), device=dev, dtype=torch.uint8)
-    ninl = torch.empty(B, device=dev, dtype=torch.int32)
-    best = torch.empty(B, device=dev, dtype=torch.int32)
-    if sigma:
-        quality = torch.empty(B, device=dev, dtype=torch.float32)
-        _lib.call("og_homography_sc", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
-                  hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), H.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
-                  best.data_ptr(), quality.data_ptr(), wp, _lib.STREAM)
-        return {"H": H, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best, "quality": quality}
-    _lib.call("og_homography", dev, B, M, N, k0.data_ptr(), k1.data_ptr(), m0.data_ptr(), _lib.ptr(nk), float(threshold),
-              hypotheses, refine, int(seed) & (2 ** 64 - 1), int(pair_offset), H.data_ptr(), inl.data_ptr(), ninl.data_ptr(),
-              best.data_ptr(), wp, _lib.STREAM)
-    return {"H": H, "inliers": inl[:, :M].bool(), "num_inliers": ninl, "best_model": best}
+    return _ransac("H", "og_homography", "og_homography_workspace_bytes", 1, keypoints0, keypoints1, matches0, num_keypoints0, threshold,
+                   hypotheses, refine, seed, pair_offset, scoring)
 
 
 def find_homography(matched_kpts0, matched_kpts1, **kw) -> Tuple[torch.Tensor, torch.Tensor]:
     """One pair as a caller passes it to cv2.findHomography: matched keypoints [K, 2] of both images -> (H [3, 3] float64 divided by
     H[2, 2] as cv2 returns it, zero without a model; inliers [K] bool).  Keyword arguments as homography (threshold, hypotheses,
     refine, seed, pair_offset, scoring).  An H whose last entry is 0 (the origin sent to infinity) has no such form and comes out non-finite."""
-    _sigma(kw.get("scoring", "inliers"))
-    s0, s1 = _shape(matched_kpts0, "matched_kpts0"), _shape(matched_kpts1, "matched_kpts1")
-    if len(s0) != 2 or s0[1] != 2 or s1 != s0:
-        raise ValueError(f"matched_kpts0 / matched_kpts1 must both be [K, 2], got {list(s0)} / {list(s1)}")
-    k0 = _lib.gpu_tensor(matched_kpts0, "matched_kpts0", convert=True)
-    k1 = _lib.gpu_tensor(matched_kpts1, "matched_kpts1", convert=True)
-    m0 = torch.arange(k0.shape[0], device=k0.device).unsqueeze(0)
-    r = homography(k0.unsqueeze(0), k1.unsqueeze(0), m0, **kw)
+    r = _find(homography, matched_kpts0, matched_kpts1, kw)
     H = r["H"][0]
     return torch.where(r["best_model"][0] >= 0, H / H[2, 2], torch.zeros_like(H)), r["inliers"][0]      # no host synchronisation
 
@@ -218,17 +194,7 @@ def homography_4pt(x0: torch.Tensor, x1: torch.Tensor):
     """The four-point minimal solver on its own: x0, x1 [count, 4, 2] correspondences (x1 ~ H x0) with coordinates of order 1
     -> (H [count, 3, 3] float64, unit Frobenius norm, largest entry positive, zero without a solution; num_solutions [count] int32,
     0 or 1)."""
-    s0, s1 = _shape(x0, "x0"), _shape(x1, "x1")
-    if len(s0) != 3 or s0[1:] != (4, 2) or s1 != s0 or not 0 < s0[0] <= 2 ** 30:
-        raise ValueError(f"x0 / x1 must both be [count, 4, 2] with 0 < count <= 2^30, got {list(s0)} / {list(s1)}")
-    a = _lib.gpu_tensor(x0, "x0", torch.float64, convert=True)
-    b = _lib.gpu_tensor(x1, "x1", torch.float64, convert=True)
-    count = a.shape[0]
-    dev = a.device
-    H = torch.empty(count, 3, 3, device=dev, dtype=torch.float64)
-    ns = torch.empty(count, device=dev, dtype=torch.int32)
-    _lib.call("og_homography_4pt", dev, count, a.data_ptr(), b.data_ptr(), H.data_ptr(), ns.data_ptr(), _lib.STREAM)
-    return H, ns
+    return _minimal("og_homography_4pt", 4, 1, x0, x1)
 
 
 def sigma_consensus(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -158,7 +158,9 @@ def test_header_and_binding_hold_the_new_entries():
 
 def test_geometry_kernels_do_not_spill(tmp_path):
     """Every kernel of geometry.hip compiles for gfx950 with 0 bytes of scratch: the solver's matrices and the refit's 45
-    accumulators are indexed at compile time and stay in registers."""
+    accumulators are indexed at compile time and stay in registers.  The six are the Fundamental instances of the RANSAC skeleton
+    (og_ransac_hartley.h), each found exactly once; the two sigma-consensus instances (SC = 1), which test_sigma_consensus_cpu.py
+    used to check in sigma_consensus.hip, are checked here."""
     src = os.path.join(og_build.CSRC, "geometry.hip")
     r = subprocess.run([og_build._hipcc(), "--offload-arch=gfx950", "-std=c++17", "-O3", "-Rpass-analysis=kernel-resource-usage",
                         "--cuda-device-only", "-c", src, "-o", str(tmp_path / "g.o")], capture_output=True, text=True)
@@ -172,7 +174,9 @@ def test_geometry_kernels_do_not_spill(tmp_path):
         if mm and name:
             usage.setdefault(name, {})[mm.group(1)] = int(mm.group(2))
     print(usage)
-    for kernel in ("fm_prep_kernel", "fm_solve_kernel", "fm_score_kernel", "fm_finish_kernel"):
+    for kernel in ("ransac_prep_kernelINS_11FundamentalEE", "ransac_solve_kernelINS_11FundamentalEE",
+                   "ransac_score_kernelINS_11FundamentalELi0E", "ransac_score_kernelINS_11FundamentalELi1E",
+                   "ransac_finish_kernelINS_11FundamentalELi0E", "ransac_finish_kernelINS_11FundamentalELi1E"):
         hits = [v for k, v in usage.items() if kernel in k]
-        assert hits and all(v["ScratchSize [bytes/lane]"] == 0 for v in hits), (kernel, usage)
-    assert len(usage) == 4, usage
+        assert len(hits) == 1 and hits[0]["ScratchSize [bytes/lane]"] == 0, (kernel, usage)
+    assert len(usage) == 6, usage
